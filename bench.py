@@ -18,7 +18,16 @@ independent until the combine, which run_metakriging.py measures).
 roofline.traffic is the PMC-measured HBM traffic of the same kernel from profiles/
 (rocprofv3 --pmc passes of this command, gfx950 FETCH_SIZE x2 correction).
 
-  python bench.py --gpus N --steps K --warmup W
+A plain run does what the headline figure needs and no more: set-up, adaptation and warmup, the
+timed window (with the roofline kernel's sampled events), the result line.  --full adds
+everything else the line can hold: the CPU baseline over the same window, the untimed per-kernel
+pass (kernels_ms_per_step, roofline_inverse, hbm_subphases), the 32-subset share, configs[1] and
+configs[3] window legs, the configs[4] kriging leg and the measured end-to-end job (each with its
+own --no-... switch).  --dump-outputs DIR writes what the last timed step computed (every subset's
+parameter sample and latent field, and its kriging draw when that step is a kept one) as
+DIR/<name>.npy (float64); the inputs are seeded, so two builds can be compared output for output.
+
+  python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
 """
 import argparse
 import os
@@ -57,9 +66,17 @@ def parse():
     ap.add_argument("--n", type=int, default=500_000)
     ap.add_argument("--subsets", type=int, default=250)
     ap.add_argument("--n-test", type=int, default=1000)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the CPU baseline, the per-kernel pass after "
+                         "the window, the extra legs and the end-to-end job (minutes; see the --no-... switches)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float64): samples (subsets x "
+                         "parameters), w (the latent fields, subset after subset) and, when that step is a kept "
+                         "iteration, w_pred (subsets x test sites, its kriging draw)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--no-legs", action="store_true",
-                    help="skip the extra legs (N=1): the 32-subset shard window and the configs[4] kriging sample")
+                    help="--full without the extra legs (N=1): the 32-subset shard window, configs[1], configs[3] "
+                         "and the configs[4] kriging sample")
     ap.add_argument("--shard-subsets", type=int, default=32,
                     help="subsets of the shard leg (the per-GPU share of configs[2] on 8 GPUs)")
     ap.add_argument("--krig-subsets", type=int, default=32, help="subsets of the configs[4] kriging leg")
@@ -80,7 +97,7 @@ def parse():
     ap.add_argument("--adapt-batches", type=int, default=6,
                     help="untimed amcmc batches of 50 before the warmup (adapted proposal scales in the window)")
     ap.add_argument("--no-e2e", action="store_true",
-                    help="skip the measured end-to-end leg (N=1: the whole configs[2] script, ~2 minutes)")
+                    help="--full without the measured end-to-end leg (N=1: the whole configs[2] script, ~2 minutes)")
     ap.add_argument("--e2e-devices", default="0",
                     help="GPUs of the end-to-end leg, one process through libmk's multi-device driver "
                          "(mk_meta_fit), e.g. 0,1,2,3,4,5,6,7 on a node")
@@ -282,6 +299,30 @@ def inverse_roofline(k):
             "source": "untimed post-window pass, every kernel kind evented"}
 
 
+def dump_outputs(ses, out_dir, w, last, suffix=""):
+    """--dump-outputs: what the timed window's last step (iteration `last`, 1-based) computed, as
+    out_dir/<name><suffix>.npy in float64 -- samples (subsets x parameters: that iteration's row of
+    p.beta.theta.samples), w (the subsets' latent fields after it, one after another; `w` was read
+    then) and, when the step is a kept one, w_pred (subsets x test sites: its kriging draw).  The
+    library hands predictive draws out of a finished chain only, so the session first runs its
+    remaining iterations (untimed).  An array above 16 MB is cut to a fixed seeded sample."""
+    cfg = ses.cfg
+    if cfg.n_samples > ses.iteration:
+        ses.run(cfg.n_samples - ses.iteration)
+    kept = last - cfg.burn_in            # 0-based kept index of iteration `last`
+    o = ses.outputs(quantiles=False, samples=True, w_pred_samples=kept >= 0)
+    arrays = {"samples": np.stack([s_[last - 1] for s_ in o["samples"]]), "w": np.concatenate(w)}
+    if "w_pred_samples" in o:
+        arrays["w_pred"] = np.stack([p_[:, kept] for p_ in o["w_pred_samples"]])
+    os.makedirs(out_dir, exist_ok=True)
+    cap = 16 * 2 ** 20 // 8
+    for name, arr in arrays.items():
+        arr = np.ascontiguousarray(arr, dtype=np.float64)
+        if arr.size > cap:
+            arr = arr.ravel()[np.sort(np.random.default_rng(20250114).choice(arr.size, cap, replace=False))]
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), arr)
+
+
 def end_to_end(mk, d, K, devices=(0,)):
     """The whole reference script on this GPU (metakriging.reference_flow -> mk_meta_fit):
     partition (R's stream) -> glm -> 5,000 amcmc iterations of every subset with spPredict on the
@@ -417,7 +458,8 @@ def main():
     if rehearse:
         local, a.no_e2e = 0, True
     K, n, n_test = a.subsets, a.n, a.n_test
-    want_cpu = rank == 0 and world == 1 and not a.no_cpu_baseline
+    want_cpu = a.full and rank == 0 and world == 1 and not a.no_cpu_baseline
+    want_legs, want_e2e = a.full and not a.no_legs, a.full and not a.no_e2e
     host = host_cores() if want_cpu else None
 
     dist = None
@@ -495,34 +537,40 @@ def main():
     st = ses.kernel_stats(mk.session.KS_UPDATE_BUSY)
     summed_ms = sts[0]["ms"] + sts[1]["ms"]
     sweep_fallbacks = ses.kernel_stats(mk.session.KS_SWEEP_FALLBACK)["launches"]
-    # per-kernel breakdown: a separate untimed pass of n_post (kept) iterations, every kind evented
-    kinds = [("chol_update", 0), ("chol_update_sub", 7), ("chol_diag", 1), ("chol_trsm", 2), ("w_sweep", 3),
-             ("qblocks", 4), ("inverse", 6), ("cov_candidate", 10)]
-    before = {name: ses.kernel_stats(i) for name, i in kinds}
-    ses.profile(True)
-    ses.run(n_post)
-    kern = {name: {"ms": ses.kernel_stats(i)["ms"] - before[name]["ms"],
-                   "flops": ses.kernel_stats(i)["flops"] - before[name]["flops"],
-                   "launches": ses.kernel_stats(i)["launches"] - before[name]["launches"]} for name, i in kinds}
+    # --dump-outputs: the latent fields as the last timed step left them (the chain moves on below)
+    dump_w = [ses.chain_state(i)["w"] for i in range(hi - lo)] if a.dump_outputs else None
+    kern = None
+    if a.full:
+        # per-kernel breakdown: a separate untimed pass of n_post (kept) iterations, every kind evented
+        kinds = [("chol_update", 0), ("chol_update_sub", 7), ("chol_diag", 1), ("chol_trsm", 2), ("w_sweep", 3),
+                 ("qblocks", 4), ("inverse", 6), ("cov_candidate", 10)]
+        before = {name: ses.kernel_stats(i) for name, i in kinds}
+        ses.profile(True)
+        ses.run(n_post)
+        kern = {name: {"ms": ses.kernel_stats(i)["ms"] - before[name]["ms"],
+                       "flops": ses.kernel_stats(i)["flops"] - before[name]["flops"],
+                       "launches": ses.kernel_stats(i)["launches"] - before[name]["launches"]} for name, i in kinds}
     dev_window = ses.outputs(quantiles=False, samples=True)["samples"][:n_cpu] if n_cpu else []
+    if a.dump_outputs:
+        dump_outputs(ses, a.dump_outputs, dump_w, W + a.steps, "" if world == 1 else f".rank{rank}")
     ses.close()
     legs = {}
-    if world == 1 and not a.no_legs:
+    if world == 1 and want_legs:
         ls = max(40, a.steps)   # the legs' windows: 40 steps at least (a 20-step window of a small shard is noisy)
         legs["configs[2]_share32"] = shard_leg(mk, d, idx, min(a.shard_subsets, K), beta0, bt, a.adapt_batches, a.warmup, ls)
         legs["configs[1]_matern"] = config_leg(mk, 1, a.adapt_batches, a.warmup, ls)
         legs["configs[3]_lmc_share7"] = config_leg(mk, 3, a.adapt_batches, a.warmup, ls, subsets=7)
     e2e = None
-    if world == 1 and not a.no_e2e:
+    if world == 1 and want_e2e:
         with _stdout_to_stderr():    # RCCL prints its version banner on stdout at communicator set-up
             e2e = end_to_end(mk, d, K, tuple(int(x) for x in a.e2e_devices.split(",")))
-    if world == 1 and not a.no_legs:
+    if world == 1 and want_legs:
         # the 1M-site kriging leg in a fresh process (bench_kriging.py: the same kriging_leg on 32
         # subsets of n_s = 2,000 from the same generator): sessions that follow one another in a process
         # can inherit the HIP runtime's queue state -- in-process, after the other legs
         # and the end-to-end leg, this leg read ~10 % low (16.9 vs 18.7-19.0 M draws/s)
         legs["configs[4]_kriging"] = kriging_leg_process(min(a.krig_subsets, K), a.krig_sites)
-    elif world > 1 and not a.no_e2e and not weak:
+    elif world > 1 and want_e2e and not weak:
         if rank == 0:
             e2e = node_end_to_end(a, world)
         dist.barrier(group=cpu_group)
@@ -600,16 +648,19 @@ def main():
                                      "shared with those kernels, so frac understates the kernel's own rate"
                                      if la else "update launches run alone on the stream (sequential schedule)")},
         "sweep_fallbacks": sweep_fallbacks,   # multi-workgroup sweep only: subsets refused admission
-        # the second MFMA kernel: W = L^-1 of the accepted factors (k_inv_level), from the post-window pass
-        "roofline_inverse": inverse_roofline(kern["inverse"]),
-        "kernels_ms_per_step": {k: v["ms"] / n_post for k, v in kern.items()},
-        "kernels_ms_per_step_note": f"untimed post-window pass of {n_post} iterations, every kernel kind evented",
-        # the HBM-bound sub-phases in GB/s, on algorithmic bytes per subset-iteration --
-        # the candidate's lower triangle written once (4 (n_s+1)^2 B), W read once by the sweep (4 n_s^2 B)
-        "hbm_subphases": hbm_subphases(kern, n_post, [len(s_["coords"]) for s_ in subs]),
         "chain_iters_per_s": a.steps / elapsed,
         "end_to_end_estimate_s": elapsed / a.steps * 5000,
     }
+    if kern is not None:      # --full: the post-window pass
+        out.update({
+            # the second MFMA kernel: W = L^-1 of the accepted factors (k_inv_level), from the post-window pass
+            "roofline_inverse": inverse_roofline(kern["inverse"]),
+            "kernels_ms_per_step": {k: v["ms"] / n_post for k, v in kern.items()},
+            "kernels_ms_per_step_note": f"untimed post-window pass of {n_post} iterations, every kernel kind evented",
+            # the HBM-bound sub-phases in GB/s, on algorithmic bytes per subset-iteration --
+            # the candidate's lower triangle written once (4 (n_s+1)^2 B), W read once by the sweep (4 n_s^2 B)
+            "hbm_subphases": hbm_subphases(kern, n_post, [len(s_["coords"]) for s_ in subs]),
+        })
     if legs:
         out["legs"] = legs
     if e2e is not None:

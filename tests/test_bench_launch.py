@@ -90,6 +90,52 @@ def test_process_group_setup_output_stays_off_stdout(capfd):
     assert out == '{"metric": 1}\n' and "[Gloo]" in err
 
 
+def test_full_and_dump_outputs_are_off_by_default():
+    m = _bench()
+    a = _args(m, ["--gpus", "1", "--steps", "5", "--warmup", "1"])
+    assert a.full is False and a.dump_outputs is None
+    a = _args(m, ["--full", "--dump-outputs", "d", "--no-e2e"])
+    assert a.full is True and a.dump_outputs == "d" and a.no_e2e
+
+
+def test_dump_outputs_writes_the_last_timed_step(tmp_path):
+    """dump_outputs finishes the chain, then writes the rows of iteration `last`: its sample, the
+    latent fields handed in and -- as `last` is a kept iteration -- its kriging draw, in float64."""
+    import numpy as np
+    m = _bench()
+    S, P, C, n_samples, burn_in, last = 3, 4, 5, 50, 18, 20
+
+    class Cfg:
+        pass
+
+    class Ses:
+        cfg = Cfg()
+        iteration = last
+        ran = []
+
+        def run(self, n):
+            self.ran.append(n)
+            self.iteration += n
+
+        def outputs(self, quantiles, samples, w_pred_samples):
+            assert self.iteration == n_samples and not quantiles and samples and w_pred_samples
+            rng = np.random.default_rng(1)
+            return {"samples": [rng.normal(size=(n_samples, P)) for _ in range(S)],
+                    "w_pred_samples": [rng.normal(size=(C, n_samples - burn_in + 1)) for _ in range(S)]}
+
+    Ses.cfg.n_samples, Ses.cfg.burn_in = n_samples, burn_in
+    ses = Ses()
+    w = [np.full(2 + i, float(i)) for i in range(S)]
+    m.dump_outputs(ses, str(tmp_path / "o"), w, last)
+    assert ses.ran == [n_samples - last]
+    ref = ses.outputs(False, True, True)
+    got = {n: np.load(tmp_path / "o" / f"{n}.npy") for n in ("samples", "w", "w_pred")}
+    assert all(g.dtype == np.float64 for g in got.values())
+    assert np.array_equal(got["samples"], np.stack([s[last - 1] for s in ref["samples"]]))
+    assert np.array_equal(got["w"], np.concatenate(w))
+    assert np.array_equal(got["w_pred"], np.stack([p[:, last - burn_in] for p in ref["w_pred_samples"]]))
+
+
 def test_roofline_traffic_profile_matches_the_dominant_kernel():
     """roofline.traffic comes from the committed PMC passes (profiles/pmc_chol_update.json): they must
     be of the kernel the line names (the fused column update) and hold a positive byte count."""
