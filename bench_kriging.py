@@ -97,7 +97,7 @@ def kriging_leg(mk, subs, coords_test, beta0, bt, kept=6, burn=14, tile=65536, k
 
 
 def interpolated_share(mk, subs, coords_test, beta0, bt, tile=65536, subset_base=0):
-    """configs[4] through the phi-interpolated replay (mk_api.hip predict_tile_cheb), measured on a real
+    """configs[4] through the phi-interpolated replay (mk_krig.hip predict_tile_cheb), measured on a real
     kept window: the fit of MK.R:83 as written (100 x 50 amcmc iterations, burn.in 3,750 -> 1,251 kept)
     on `subs` with the test sites, then the first two test tiles' replay + 200-level grids (the first
     also makes every kept state's g = W' z, once per window).  Returns the measured phases, the

@@ -1,5 +1,6 @@
-// Library-internal interface between the session (mk_api.hip) and the multi-device driver
-// (mk_multi.hip): a shard's quantile grids stay in HBM for the device-to-device combine.
+// Library-internal interface between the session (mk_api.hip, mk_pool.hip) and the multi-device
+// driver (mk_multi.hip): a shard's quantile grids stay in HBM for the device-to-device combine.
+// What the session's own sources share is in mk_session.hpp.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <string>

@@ -1,4 +1,4 @@
-// Kernel declarations shared by the launch code (mk_api.hip).
+// Kernel declarations shared by the launch code (the host sources behind mk_session.hpp).
 #pragma once
 #include "mk_types.hpp"
 #include "mk_corr.hpp"

@@ -1,0 +1,331 @@
+// What libmk's host sources share: struct mk_session and the functions that cross files.
+//
+//   mk_api.hip       the C ABI of a session: create / run / destroy, getters, outputs, the shard interface
+//   mk_pool.hip      the process-wide stream pool
+//   mk_schedule.hip  the per-iteration launch schedule (Cholesky forms, inverse, sweep, lookahead)
+//   mk_krig.hip      the kriging buffers, the phi tables and the tiled replay
+//   mk_summary.hip   stateless entry points (combine, Weiszfeld, posterior summary, glm): no session
+//   mk_parity.hip    parity-test entry points
+//
+// mk_internal.hpp stays the interface towards mk_multi.hip and mk_watch.hip.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <algorithm>
+#include <cstdlib>
+#include <string>
+#include <utility>
+#include <vector>
+#include "../../include/mk.h"
+#include "mk_kernels.hpp"
+#include "mk_internal.hpp"
+
+namespace mk {
+int set_err(int code, const std::string& msg);   // mk_api.hip: sets mk_last_error(), returns code
+}
+
+#define HIPCHK(x)                                                                                         \
+  do {                                                                                                    \
+    hipError_t e_ = (x);                                                                                  \
+    if (e_ != hipSuccess) return ::mk::set_err(MK_E_HIP, std::string(#x " -> ") + hipGetErrorString(e_)); \
+  } while (0)
+
+// Entry of a C-ABI call that works on `dev`: registered with the stall watchdog, the caller's
+// current device restored on every return path (an R or torch host keeps its own device).
+#define MK_ENTRY_DEVICE(dev)        \
+  ::mk::ApiCall mk_call_(__func__); \
+  ::mk::DeviceGuard mk_dg_;         \
+  HIPCHK(hipSetDevice(dev))
+
+namespace mk {
+
+static inline int round_up(int a, int b) { return (a + b - 1) / b * b; }
+
+// An integer environment switch (dflt when unset or empty).
+static inline int env_int(const char* name, int dflt) {
+  const char* v = std::getenv(name);
+  return (v && *v) ? std::atoi(v) : dflt;
+}
+
+constexpr int NKSTAT = 14;
+// KS_CHOL_UPDATE: the 128-tile panel-update launches (k_chol_update<128>); KS_CHOL_UPDATE_SUB:
+// the 64- / 32-sub-tile ones (small grids).  Together: the roofline kernel k_chol_update.
+// KS_UPDATE_BUSY: both, with the time of launches that overlap (the split schedule's bulk and
+// critical streams) counted once -- the union of their event intervals.
+// KS_PRED_VAR: the kriging GEMM k_pred_var; its flops assume every pair is refreshed (an upper
+// bound: only the pairs whose factor changed are in the list -- bench_kriging counts exactly).
+// KS_COV: the candidates' covariance assembly (k_cov_candidate, with k_matern_table for Matern).
+enum { KS_CHOL_UPDATE = 0, KS_CHOL_DIAG, KS_CHOL_TRSM, KS_SWEEP, KS_LAUUM, KS_ITER, KS_INV, KS_CHOL_UPDATE_SUB,
+       KS_UPDATE_BUSY, KS_PRED_VAR, KS_COV, KS_SWEEP_FALLBACK, KS_KRIG_CHEB, KS_KRIG_FALLBACK };
+// KS_KRIG_CHEB: tiles kriged by phi interpolation (predict_tile_cheb): launches = tiles, flops = exact
+// s evaluations ((subset, node or check point) pairs), total_ms = the largest check difference seen
+// (not a time).  KS_KRIG_FALLBACK: tiles whose check failed and were replayed exactly (launches), and
+// total_ms the largest failing difference.
+// KS_SWEEP_FALLBACK: launches = (subset, iteration) sweeps k_sweep_mg refused admission and its
+// k_sweep fallback ran (counted on the device, read at the end of every mk_session_run; no timing).
+
+struct Stat {
+  long launches = 0;
+  double ms = 0.0, flops = 0.0;
+};
+
+struct Timed {
+  int which;
+  hipEvent_t a, b;
+  double flops;
+  int cnt = -1;   // >= 0: flops are per listed factor, times the device-side count copied to inv_cnt[cnt]
+};
+
+// One stream's share of the shard: views of the shard arrays starting at subset s0.
+struct Group {
+  Model md{};
+  MatSet ms{};
+  hipStream_t stream = nullptr;
+  int S = 0, s0 = 0;
+  int* d_list = nullptr;   // pairs whose factor changed (inverse work list)
+  int* d_count = nullptr;
+  int* d_plist = nullptr;  // pairs needing a kriging refresh
+  int* d_pcount = nullptr;
+  hipEvent_t done = nullptr;         // fork-join sweep: this group's pre-sweep work is queued
+  hipStream_t bulk = nullptr;        // split Cholesky (launch_cholesky): CU-masked bulk-update stream
+  std::vector<hipEvent_t> ev;        // 2 nt + 1 events reused every factorisation
+};
+
+// Scoped device scratch (freed on every return path).
+struct DevBufs {
+  std::vector<void*> p;
+  ~DevBufs() {
+    for (void* x : p) hipFree(x);
+  }
+  template <typename T>
+  T* get(size_t n) {
+    void* x = nullptr;
+    if (hipMalloc(&x, std::max<size_t>(n, 1) * sizeof(T)) != hipSuccess) {
+      (void)hipGetLastError();   // not sticky for the caller's later launch checks
+      return nullptr;
+    }
+    p.push_back(x);
+    return (T*)x;
+  }
+};
+
+// ---- mk_pool.hip: streams by device and kind (plain, high priority, CU-masked with a given mask)
+enum { SK_PLAIN = 0, SK_PRIO = 1, SK_CUMASK = 2 };
+struct PoolKey {
+  int device = -1, kind = SK_PLAIN, prio = 0;
+  std::vector<uint32_t> mask;
+  bool operator==(const PoolKey& o) const {
+    return device == o.device && kind == o.kind && prio == o.prio && mask == o.mask;
+  }
+};
+typedef std::vector<std::pair<PoolKey, hipStream_t>> StreamList;
+
+// ---- the sub-systems of a session, each with the file that owns it
+
+// mk_schedule.hip (run_iteration_la).  Lookahead schedule (one group): iteration t+1's phi
+// candidates are factored on c while iteration t's inverse and sweep run on the main stream,
+// and their z' = L'^-1 u is solved on the main stream trailing the factorisation panel by panel.
+struct Lookahead {
+  int mode = -1;               // mk_session_set_lookahead: -1 auto, 0 off, 1 on
+  bool ok = false;             // eligible (buffers allocated)
+  bool on = false;             // in use
+  int next = -1;               // iteration whose candidates are queued on c (-1: none)
+  int enq = 0;                 // panels of those candidates enqueued so far
+  hipStream_t m = nullptr;     // MK_LA_MASK: CU-masked main stream of the lookahead iterations
+  hipStream_t c = nullptr;     // created at the first lookahead run (an unused stream still takes a
+                               // hardware queue, GPU_MAX_HW_QUEUES = 4, and slows the split Cholesky)
+  hipStream_t k = nullptr;     // kept iterations' kriging refresh beside the sweep
+  std::vector<hipEvent_t> ev;  // [nt] panel k final | decided (or adapted) | join | W ready | kriged
+};
+
+// mk_schedule.hip (iteration_pre_sweep).  Sequential schedule, one group (MK_EARLY_COV, default on):
+// iteration t+1's phi candidates are assembled (without the bordered row) on st beside iteration t's
+// sweep; iteration t+1 writes the row once its A step has produced u (k_cand_border) and factors as
+// usual -- the same matrices.
+struct EarlyCov {
+  int pre = -1;                // iteration whose candidates st has assembled (-1: none)
+  hipStream_t st = nullptr;
+  hipEvent_t ev[2] = {nullptr, nullptr};   // [0] main stream ready for it, [1] assembled
+};
+
+// mk_krig.hip (krig_tables).  Fused kriging from phi tables (exponential, q = 1, one group):
+// s(t; phi) at Chebyshev nodes of the prior's phi range, made at session creation; kept iterations
+// interpolate them.
+struct KrigTables {
+  bool on = false;
+  int fail = 0;                // set-up checks that failed (the session then refreshes X exactly)
+  double check = 0.0, evals = 0.0;
+  ChebK tab{};
+  double* g = nullptr;         // [S][n_pad] g = W' z of the current kept iteration
+  double* z = nullptr;         // [S][n_pad + 2]: its z, then phi and A per subset (k_kt_snap)
+  hipEvent_t ev[2] = {nullptr, nullptr};   // [0] snapshot taken, [1] draws done (side stream)
+  bool pending = false;        // draws queued on the side stream, not yet waited for
+};
+
+// mk_krig.hip (predict_tile_cheb).  Phi-interpolated tiled kriging: the window's g_k = W_k' z_k and
+// phi_k, kept across tiles (made at the first tile after a run or a window change).
+struct ChebWindow {
+  double* G = nullptr;         // [S][n_pad][nkp]: g of the window's states (nkp = window rounded up to 8)
+  double* phi = nullptr;       // [win][S]
+  double* phit = nullptr;      // [S][nkp]: phi per state, padded with the last
+  std::vector<double> phi_h;
+  int iter = -1, lo = -1, n = -1;
+};
+
+// mk_api.hip (plan_sweep) chooses, mk_schedule.hip (launch_sweep) launches.  site: the one-pass site
+// sweep (default; row pairs per thread, 0: off) with its LDS and lean form; else, for multi-outcome
+// small shards, the split-launch multi-workgroup kernel behind its admission consensus, k_sweep
+// sweeping the subsets it did not admit (coop), or the split-launch sweep (split: no inter-workgroup
+// waits); else the 64-site-block kernel (k_sweep, one workgroup per subset).
+struct SweepPlan {
+  int site = 0;
+  size_t site_lds = 0;
+  int lean = 0;                // q = 1: 1 border row by factor, 2 every n_s even (sweep_site_kernel)
+  bool split = false;          // k_sweep_step, one launch per 64-site block
+  bool coop = false;           // k_sweep_mg (admission consensus) + k_sweep for the subsets not admitted
+  size_t mg_lds = 0;
+  double* sp_part = nullptr;
+  double* sw_part = nullptr;
+  int* sw_cnt = nullptr;       // [S][n_pad / 64] block counters, then [S] admission words (sw_adm)
+  int* sw_adm = nullptr;
+  int adm_spins = MK_ADM_SPINS;
+  int* sw_xcc = nullptr;
+  int* sw_err = nullptr;
+};
+
+// mk_schedule.hip (timed, drain_timers).
+struct Profiler {
+  bool on = false;
+  uint32_t kinds = ~0u;   // kernel kinds bracketed by events while on (bit per KS_ kind)
+  int every = 1;          // bracket the launches of every every-th iteration only
+  bool iter = true;       // this iteration's launches are bracketed (mk_session_run)
+  std::vector<Timed> pending;
+  // KS_INV timing: the inverse's work list length lives on the device, so each timed inverse copies
+  // its count into a pinned slot in stream order; drain_timers prices the launches with it
+  static constexpr int INV_CNT_CAP = 65536;
+  int* inv_cnt = nullptr;
+  int inv_cnt_used = 0;
+  Stat stats[NKSTAT];
+};
+
+}  // namespace mk
+
+struct mk_session {
+  mk_session();
+  ~mk_session();   // mk_api.hip: the teardown order
+  int device = 0;
+  hipStream_t stream = nullptr;   // set-up, outputs and the one-group paths
+  mk::StreamList owned;           // every stream of the session (pool_stream), back to the pool at the end
+  mk::Model md{};
+  mk::MatSet ms{};
+  int S = 0, q = 1, p = 0, n_pad = 0, nt = 0, P = 0;
+  int iter = 0;
+  bool matern = false, record_samples = true, record_w = false;
+  bool pred_gen = false;          // kriging P^T generated inside k_pred_var (exponential; no P^T buffer)
+  mk::Group all;                  // the whole shard on `stream`
+  std::vector<mk::Group> groups;  // the run-time split, one stream each
+  hipEvent_t swept = nullptr;     // fork-join sweep (several groups): the whole-shard sweep is queued
+  bool tiled = false;             // kriging after the fit over test-site tiles (predict_tile)
+  int pred_tile = 0, n_test_all = 0, n_test_pad_all = 0;
+  int tile_req = 0;               // predict_tile as configured
+  int win_lo = 0, win_n = -1;     // tiled kriging: kept states [win_lo, win_lo + win_n) (-1: all)
+  std::vector<double> span_pt_h;  // [S] bound on the subset-site to test-site distances (host copy)
+  std::vector<void*> kbufs;       // the kriging buffers (re-sized by mk_session_set_test_sites)
+  std::vector<double> bbox;       // [S][4] xmin xmax ymin ymax of each subset's sites (Matern table ranges)
+  double* d_ct_all = nullptr;     // all test sites [2][n_test_pad_all] (tiled mode)
+  int* d_slist = nullptr;         // tiled replay: per-outcome subset lists [q][S] + counts [q]
+  int* d_run_start = nullptr;     // tiled replay, q = 1: first window state of each subset's pending draws
+  int* d_scount = nullptr;
+  double* d_probs = nullptr;
+  mk::Lookahead la;
+  mk::EarlyCov cov;
+  mk::KrigTables kt;
+  mk::ChebWindow cg;
+  mk::SweepPlan sweep;
+  mk::Profiler prof;
+  hipError_t launch_err = hipSuccess;   // first failed kernel launch of a run
+  const char* poisoned = nullptr;       // set when a run left the chain in a state that is not the sampler's
+  std::vector<int> n_part;
+  std::vector<void*> allocs;
+
+  // Free one buffer allocated by alloc().
+  void release(void* ptr) {
+    if (!ptr) return;
+    for (size_t i = 0; i < allocs.size(); ++i)
+      if (allocs[i] == ptr) {
+        hipFree(ptr);
+        allocs.erase(allocs.begin() + (long)i);
+        return;
+      }
+  }
+  template <typename T>
+  int alloc(T** p_, size_t n) {
+    void* ptr = nullptr;
+    if (n == 0) n = 1;
+    hipError_t e = hipMalloc(&ptr, n * sizeof(T));
+    if (e != hipSuccess) {
+      (void)hipGetLastError();   // the failed malloc is sticky in hipGetLastError: clear it for later calls
+      return mk::set_err(MK_E_NOMEM, std::string("hipMalloc ") + std::to_string(n * sizeof(T)) + " B");
+    }
+    allocs.push_back(ptr);
+    *p_ = (T*)ptr;
+    return 0;
+  }
+};
+
+namespace mk {
+
+static inline hipEvent_t ev_new() {
+  hipEvent_t e;
+  hipEventCreate(&e);
+  return e;
+}
+
+// Launch helper that optionally brackets a kernel with events on its stream.
+template <typename F>
+static void timed(mk_session* s, hipStream_t st, int which, double flops, F&& launch, int cnt = -1) {
+  if (!s->prof.on || !s->prof.iter || !((s->prof.kinds >> which) & 1u)) {
+    launch();
+    return;
+  }
+  Timed t{which, ev_new(), ev_new(), flops, cnt};
+  hipEventRecord(t.a, st);
+  launch();
+  hipEventRecord(t.b, st);
+  s->prof.pending.push_back(t);
+}
+
+// ---- mk_api.hip
+Model model_view(const Model& m, int s0, int S);   // subsets [s0, s0 + S) of the shard's arrays
+MatSet matset_view(const MatSet& m, int s0);
+int setup_groups(mk_session* s, int n_groups);
+
+// ---- mk_pool.hip
+// A stream of this kind on the current device (hipSetDevice(device) done by the caller), recorded
+// in `owned` for the session's destructor; pool_return hands every stream of `owned` back, drained.
+hipError_t pool_stream(StreamList& owned, hipStream_t* st, int device, int kind, int prio = 0,
+                       const std::vector<uint32_t>& mask = {});
+void pool_return(StreamList& owned);
+int hw_queues();   // hardware queues of this process's HIP runtime
+
+// ---- mk_schedule.hip
+void drain_timers(mk_session* s);
+bool set_gemm_lds();
+int launch_quantiles(unsigned grid, hipStream_t st, const double* data, long subset_stride, long row_stride,
+                     int n_rows, int n_cols, const double* probs, int n_probs, double* out);
+void launch_candidates(const Model& md, const MatSet& ms, hipStream_t st, int n_entries, int h0, int hc, int which,
+                       int iter, const int* slist = nullptr, const int* scount = nullptr);
+void launch_cholesky(mk_session* s, Group& g, int h0, int hc, const int* slist = nullptr, const int* scount = nullptr,
+                     hipStream_t crit = nullptr, hipEvent_t* evP = nullptr, int k_lo = 0, int k_hi = -1);
+void launch_trinv(mk_session* s, Group& g, int max_entries, const int* list, const int* count);
+void launch_inverse(mk_session* s, Group& g, bool from_zc = false);
+void launch_pred_refresh(mk_session* s, Group& g, hipStream_t st = nullptr);
+bool la_auto(const mk_session* s);   // the default schedule of this shard is the lookahead one
+void run_iteration(mk_session* s, int it);
+
+// ---- mk_krig.hip
+int kriging_buffers(mk_session* s, int n_test_all, const double* coords_test);
+int krig_tables(mk_session* s);
+int predict_tile(mk_session* s, int t0, double* dq, mk_outputs* o);
+int predict_tiled(mk_session* s, mk_outputs* o);
+
+}  // namespace mk

@@ -1,5 +1,5 @@
 """The kriging variance by phi interpolation (MK.R:87-89): the tiled replay
-(spPredict after the fit, mk_api.hip predict_tile_cheb) and the fused path's phi tables (krig_tables).
+(spPredict after the fit, mk_krig.hip predict_tile_cheb) and the fused path's phi tables (krig_tables).
 
 The kriging variance s(t; phi) = rho_t(phi)' R(phi)^-1 rho_t(phi) is computed exactly at Chebyshev
 nodes of each subset's kept phi range and interpolated at every kept state's phi; the mean is
@@ -112,7 +112,7 @@ def test_interpolated_kriging_matches_the_oracle(mk, monkeypatch):
     np.testing.assert_allclose(dev["w_predict_sum"][:, sites], grid_sum, rtol=0, atol=2 * TOL)
 
 
-# ---- the fused path's phi tables (mk_api.hip krig_tables): s(t; phi) tabulated over the prior's phi
+# ---- the fused path's phi tables (mk_krig.hip krig_tables): s(t; phi) tabulated over the prior's phi
 # range at session creation; kept iterations draw with g = W' z and the interpolated s
 
 def _fused(mk, monkeypatch, subs, ct, cfg, mode, base=0, lookahead=-1):

@@ -1,4 +1,4 @@
-"""libmk's stream pool (mk_api.hip pool_stream): sessions take their HIP streams -- the plain ones,
+"""libmk's stream pool (mk_pool.hip pool_stream): sessions take their HIP streams -- the plain ones,
 the lookahead schedule's high-priority candidate stream and its CU-masked main stream, the split
 Cholesky's CU-masked bulk stream -- from a per-process pool and hand them back drained.  Many short
 sessions in a row (a test suite's pattern) must each replay the same chain on reused streams."""

@@ -6,7 +6,7 @@ run's chains), with the reference's sampler as written -- 100 x 50 amcmc iterati
 1,251 kept states (MK.R:57-59, 83, 85) -- through the tiled replay (predict_tile = 65,536): per test
 tile, the replay of all 1,251 kept states (X = W P^T re-run where phi changed), the 200-level grids
 of every subset and their sequential mean over the shard (the shard's share of the combine, MK.R:123-133).
-Since round 6 the replay interpolates the kriging variance in phi (MK_KRIG_CHEB, mk_api.hip
+Since round 6 the replay interpolates the kriging variance in phi (MK_KRIG_CHEB, mk_krig.hip
 predict_tile_cheb); MK_KRIG_CHEB=0 runs the exact replay.
 
 Wall clock by phase.  One gpurun command may run at most 20 minutes, so the 16 test tiles can be
