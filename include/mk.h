@@ -45,6 +45,9 @@ typedef struct mk_problem {
   const double* x;            /* concatenated per subset: (n_s*q) x p column-major    */
   int32_t n_test;             /* held-out sites (coords.test rows)                    */
   const double* coords_test;  /* n_test x 2 column-major                              */
+  const double* x_test;       /* (q*n_test) x p column-major, location-major rows: x.test
+                                 (MK.R:87 spPredict's pred.covars), or NULL -- without it no
+                                 predictive probability (p_predict ...) can be asked for   */
 } mk_problem;
 
 /* spMvGLM arguments (MK.R:56-64, 80-85).  Tuning values are proposal
@@ -99,6 +102,11 @@ typedef struct mk_outputs {
   double* w_predict_sum; /* 200 x (q*n_test): w_predict summed over this call's subsets in subset
                            order -- this shard's term of the combine (MK.R:129-132) without the
                            per-subset grids on the host                                          */
+  /* spPredict's p.y.predictive.samples for the binomial family: p = linkinv(x(s)'beta + w(s)) of
+   * every kept state, beta and w(s) of the same iteration.  They need x_test (MK_E_ARG without). */
+  double* p_predict;    /* [n_subsets] x (200 x q*n_test): the 200-level grids of p, as w_predict      */
+  double* p_pred_samples; /* [n_subsets] x ((q*n_test) x kept): the p draws, as w_pred_samples          */
+  double* p_predict_sum; /* 200 x (q*n_test): p_predict summed in subset order, as w_predict_sum        */
 } mk_outputs;
 
 typedef struct mk_session mk_session;
@@ -138,10 +146,14 @@ int mk_session_outputs(mk_session* s, mk_outputs* out);
  * mk_session_outputs to iterations first..last (1-based, burn_in <= first <= last <= n.samples;
  * spPredict's start / end).  The draws are those a session with burn_in = first would make. */
 int mk_session_set_test_sites(mk_session* s, int32_t n_test, const double* coords_test);
+/* Covariates of the session's current test sites: x_test (q*n_test) x p column-major (spPredict's
+ * pred.covars), copied to HBM; the p_* outputs and the p grids need them.  mk_session_set_test_sites
+ * drops them (new sites need their own).  MK_E_ARG when the session has no test sites. */
+int mk_session_set_test_covars(mk_session* s, const double* x_test);
 int mk_session_set_kept_window(mk_session* s, int32_t first, int32_t last);
 /* After all iterations: the shard's 200-level grids, [n_subsets] x (200 x C) column-major -- which 0:
  * obj[[i]]$parameters (C = P), which 1: obj[[i]]$w.predict (C = q*n_test; fused sessions, tiled ones
- * use mk_session_tile_grids) -- into out: host memory, or HBM of the session's device when
+ * use mk_session_tile_grids), which 2: the p.predict grids (as 1; needs x_test) -- into out: host memory, or HBM of the session's device when
  * device_out != 0 (e.g. the send buffer of a device-resident combine; no host round trip). */
 int mk_session_grids(mk_session* s, int32_t which, double* out, int32_t device_out);
 /* Tiled sessions (predict_tile > 0), after all iterations: the 200-level w.predict grids of the test
@@ -151,6 +163,10 @@ int mk_session_grids(mk_session* s, int32_t which, double* out, int32_t device_o
  * only (spPredict, MK.R:87-89), so a host can combine tile by tile: at configs[4] the per-subset
  * grids of all 1M sites never coexist. */
 int mk_session_tile_grids(mk_session* s, int32_t t0, double* out, int32_t device_out);
+/* The same with the tile's p.predict grids: one replay of the tile writes the w grids into out_w and
+ * the grids of p = linkinv(x(s)'beta + w(s)) into out_p (same shape; needs x_test).  Either pointer
+ * may be NULL.  The next tile overwrites the draws, so both grids come from this one replay. */
+int mk_session_tile_grids_wp(mk_session* s, int32_t t0, double* out_w, double* out_p, int32_t device_out);
 /* Per-kernel timing (HIP events on the launching streams): launches, total ms and
  * algorithmic flops per kernel kind.  0: the 128-tile column-update launches -- k_chol_update_trsm
  * (column k's update of tiles k+1.. with the panel solve fused in its epilogue, plus the next diagonal
@@ -198,7 +214,9 @@ int mk_fit_predict_batched(const mk_problem* prob, const mk_config* cfg, mk_outp
  * kriging (predict_tile) exchanges the grids of one test-site tile at a time, so the configs[4]
  * combine of 1M sites needs K x 200 x q*tile doubles per device, not K x 200 x q*n_test.
  * out (optional, any field NULL): the per-subset outputs of all K subsets as mk_session_outputs
- * lays them out; out->w_predict_sum = the sequential sum of all K w.predict grids. */
+ * lays them out; out->w_predict_sum = the sequential sum of all K w.predict grids.  prob->x_test (shared
+ * by every block, as the test sites are) gives out->p_predict / p_pred_samples / p_predict_sum and
+ * comb->result3 by the same route. */
 #define MK_COMBINE_MEAN 0     /* MK.R:123-133 */
 #define MK_COMBINE_MEDIAN 1   /* north-star extension: per column Weiszfeld geometric median in W2 */
 typedef struct mk_combined {
@@ -210,6 +228,9 @@ typedef struct mk_combined {
   int32_t exchange;   /* out: 1 = RCCL, 0 = device copies                                           */
   int32_t comm_ranks; /* out: ranks of the exchange (RCCL: ncclCommCount of the communicators; copies:
                        * the number of device blocks)                                               */
+  double* result3;    /* 200 x (q*n_test): the combined p.predict grid (the subsets' grids of
+                       * p(y = 1) at the test sites, combined by `method` as result2), or NULL;
+                       * needs prob->x_test                                                         */
 } mk_combined;
 /* Progress between batches: iterations done so far (a multiple of batch_length) of n_samples. */
 typedef int (*mk_progress_fn)(void* user, int32_t iterations, int32_t n_samples);

@@ -10,7 +10,7 @@ from .session import SamplerConfig, Session, cholesky_batched, combine, correlat
 from .spbayes import spMvGLM, spPredict  # noqa: F401
 from .glm import glm_binomial  # noqa: F401
 from .post import combine_median  # noqa: F401
-from .metakriging import (combine_results, meta_fit, partition, partitioned_spMvGLM,  # noqa: F401
+from .metakriging import (combine_predictive, combine_results, meta_fit, partition, partitioned_spMvGLM,  # noqa: F401
                           posterior_summary, start_values, subset_data)
 from .node import meta_fit_node  # noqa: F401
 from . import synthetic  # noqa: F401

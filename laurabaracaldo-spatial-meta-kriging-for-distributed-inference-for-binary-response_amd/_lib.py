@@ -40,7 +40,7 @@ class MkError(RuntimeError):
 class Problem(ctypes.Structure):
     _fields_ = [("n_subsets", ctypes.c_int32), ("subset_base", ctypes.c_int32), ("q", ctypes.c_int32),
                 ("p", ctypes.c_int32), ("n_part", _ip), ("coords", _dp), ("y", _dp), ("weights", _dp),
-                ("x", _dp), ("n_test", ctypes.c_int32), ("coords_test", _dp)]
+                ("x", _dp), ("n_test", ctypes.c_int32), ("coords_test", _dp), ("x_test", _dp)]
 
 
 class Config(ctypes.Structure):
@@ -57,7 +57,8 @@ class Config(ctypes.Structure):
 
 class Outputs(ctypes.Structure):
     _fields_ = [("parameters", _dp), ("w_predict", _dp), ("samples", _dp), ("w_samples", _dp),
-                ("w_pred_samples", _dp), ("acceptance", _dp), ("w_predict_sum", _dp)]
+                ("w_pred_samples", _dp), ("acceptance", _dp), ("w_predict_sum", _dp), ("p_predict", _dp),
+                ("p_pred_samples", _dp), ("p_predict_sum", _dp)]
 
 
 class Summary(ctypes.Structure):
@@ -67,7 +68,7 @@ class Summary(ctypes.Structure):
 
 class Combined(ctypes.Structure):
     _fields_ = [("result", _dp), ("result2", _dp), ("method", ctypes.c_int32), ("max_iter", ctypes.c_int32),
-                ("tol", ctypes.c_double), ("exchange", ctypes.c_int32), ("comm_ranks", ctypes.c_int32)]
+                ("tol", ctypes.c_double), ("exchange", ctypes.c_int32), ("comm_ranks", ctypes.c_int32), ("result3", _dp)]
 
 
 # int (*mk_progress_fn)(void* user, int32_t iterations, int32_t n_samples)
@@ -85,6 +86,9 @@ EXPORTS = {
     "mk_session_lookahead": (ctypes.c_int32, [ctypes.c_void_p]),
     "mk_session_outputs": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(Outputs)]),
     "mk_session_set_test_sites": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(ctypes.c_double)]),
+    "mk_session_set_test_covars": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double)]),
+    "mk_session_tile_grids_wp": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
+                                                ctypes.c_int32]),
     "mk_session_grids": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32]),
     "mk_session_tile_grids": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32]),
     "mk_session_set_kept_window": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32]),

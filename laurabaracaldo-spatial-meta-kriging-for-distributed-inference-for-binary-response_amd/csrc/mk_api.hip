@@ -176,6 +176,7 @@ static int check_cfg(const mk_problem* pr, const mk_config* c) {
   if (pr->p < 1) return set_err(MK_E_ARG, "p must be >= 1");
   if (!pr->n_part || !pr->coords || !pr->y || !pr->weights || !pr->x) return set_err(MK_E_ARG, "null data pointer");
   if (pr->n_test < 0 || (pr->n_test > 0 && !pr->coords_test)) return set_err(MK_E_ARG, "bad coords_test");
+  if (pr->x_test && pr->n_test == 0) return set_err(MK_E_ARG, "x_test needs test sites (n_test = 0)");
   if (c->cov_model != MK_COV_EXPONENTIAL && c->cov_model != MK_COV_MATERN) return set_err(MK_E_ARG, "cov.model must be exponential or matern");
   if (c->n_batch < 1 || c->batch_length < 1) return set_err(MK_E_ARG, "n.batch and batch.length must be >= 1");
   const int n_samples = c->n_batch * c->batch_length;
@@ -663,6 +664,8 @@ extern "C" int mk_session_create(const mk_problem* pr, const mk_config* c, mk_se
   // fused kriging tables before the initial factorisation: their evaluation uses the factor slots and
   // W as scratch
   if ((rc = krig_tables(s)) || (rc = reset_factor_state(s)) || (rc = initial_state(s))) return rc;
+  // the test sites' covariates last: the kriging tile was sized from the HBM the allocations above left
+  if (pr->x_test && (rc = set_test_covars(s, pr->x_test))) return rc;
   // default schedule: lookahead where eligible; MK_LOOKAHEAD=0 / 1 overrides (mk_session_set_lookahead too)
   static const int la_env = env_int("MK_LOOKAHEAD", -1);
   s->la.on = s->la.ok && (la_env == 1 || (la_env < 0 && la_auto(s)));
@@ -873,48 +876,75 @@ int session_wpred_grids(mk_session* s, double* d_out) {
   HIPCHK(hipStreamSynchronize(s->stream));
   return 0;
 }
-// Tiled session: the grids [S][q Tc][200] of test-site tile [t0, t0 + Tc) into d_out (and the
-// tile's draws into o->w_pred_samples when set).
-int session_tile_grids(mk_session* s, int t0, double* d_out, mk_outputs* o) {
+// [S][q n_test][200] p.predict grids of a fused session into d_out: the quantiles of
+// p = pred_prob(draw), transformed as the sort's LDS is filled (no buffer of p draws).
+int session_ppred_grids(mk_session* s, double* d_out) {
+  MK_ENTRY_DEVICE(s->device);
+  Model& md = s->md;
+  if (s->tiled) return set_err(MK_E_ARG, "tiled sessions produce their grids per tile");
+  if (!s->d_xt) return set_err(MK_E_ARG, "predictive probabilities need x_test");
+  if (s->iter < md.n_samples) return set_err(MK_E_ARG, "quantile outputs need all n.samples iterations");
+  const int C = s->q * md.n_test;
+  const int rq = launch_quantiles_prob(s->S * C, s->stream, md.w_pred, (long)md.n_kept * C, (long)C, md.n_kept, C,
+                                       s->d_probs, MK_N_LEVELS, d_out, prob_src(s, 0));
+  if (rq) return rq;
+  HIPCHK(hipStreamSynchronize(s->stream));
+  return 0;
+}
+// Tiled session: the grids [S][q Tc][200] of test-site tile [t0, t0 + Tc) into d_out, those of the
+// predictive probabilities into d_out_p (either may be NULL; one replay), and the tile's draws
+// into o->w_pred_samples / o->p_pred_samples when set.
+int session_tile_grids(mk_session* s, int t0, double* d_out, mk_outputs* o, double* d_out_p) {
   MK_ENTRY_DEVICE(s->device);
   if (!s->tiled) return set_err(MK_E_ARG, "not a tiled session");
   if (s->iter < s->md.n_samples) return set_err(MK_E_ARG, "quantile outputs need all n.samples iterations");
   if (t0 < 0 || t0 >= s->n_test_all || t0 % s->pred_tile) return set_err(MK_E_ARG, "bad tile offset");
-  return predict_tile(s, t0, d_out, o);
+  return predict_tile(s, t0, d_out, o, d_out_p);
 }
 }  // namespace mk
 
 extern "C" int mk_session_grids(mk_session* s, int32_t which, double* out, int32_t device_out) {
   if (!s || !out) return set_err(MK_E_ARG, "null session/output");
   if (s->poisoned) return set_err(MK_E_HIP, std::string("session unusable after an earlier failure: ") + s->poisoned);
-  if (which != 0 && which != 1) return set_err(MK_E_ARG, "which must be 0 (parameters) or 1 (w.predict)");
-  if (which == 1 && s->tiled) return set_err(MK_E_ARG, "tiled sessions give w.predict grids per tile (mk_session_tile_grids)");
-  if (which == 1 && s->md.n_test < 1) return set_err(MK_E_ARG, "the session has no test sites");
+  if (which < 0 || which > 2) return set_err(MK_E_ARG, "which must be 0 (parameters), 1 (w.predict) or 2 (p.predict)");
+  if (which >= 1 && s->tiled) return set_err(MK_E_ARG, "tiled sessions give their kriging grids per tile (mk_session_tile_grids)");
+  if (which >= 1 && s->md.n_test < 1) return set_err(MK_E_ARG, "the session has no test sites");
+  if (which == 2 && !s->d_xt) return set_err(MK_E_ARG, "p.predict grids need x_test");
   const long C = which == 0 ? (long)s->P : (long)s->q * s->md.n_test;
   MK_ENTRY_DEVICE(s->device);
   DevBufs scratch;
   double* d = out;
   if (!device_out && !(d = scratch.get<double>((size_t)s->S * C * MK_N_LEVELS))) return set_err(MK_E_NOMEM, "grid scratch");
-  const int rc = which == 0 ? session_param_grids(s, d) : session_wpred_grids(s, d);
+  const int rc = which == 0 ? session_param_grids(s, d) : which == 1 ? session_wpred_grids(s, d) : session_ppred_grids(s, d);
   if (rc) return rc;
   if (!device_out) HIPCHK(hipMemcpy(out, d, (size_t)s->S * C * MK_N_LEVELS * 8, hipMemcpyDeviceToHost));
   return 0;
 }
 
-extern "C" int mk_session_tile_grids(mk_session* s, int32_t t0, double* out, int32_t device_out) {
-  if (!s || !out) return set_err(MK_E_ARG, "null session/output");
+extern "C" int mk_session_tile_grids_wp(mk_session* s, int32_t t0, double* out_w, double* out_p, int32_t device_out) {
+  if (!s || (!out_w && !out_p)) return set_err(MK_E_ARG, "null session/output");
   if (s->poisoned) return set_err(MK_E_HIP, std::string("session unusable after an earlier failure: ") + s->poisoned);
   if (!s->tiled) return set_err(MK_E_ARG, "tile grids need a session created with predict_tile > 0");
-  if (device_out) return session_tile_grids(s, t0, out, nullptr);
+  if (out_p && !s->d_xt) return set_err(MK_E_ARG, "p.predict grids need x_test");
+  if (device_out) return session_tile_grids(s, t0, out_w, nullptr, out_p);
   const long Tc = std::min(s->pred_tile, s->n_test_all - t0);
+  const size_t n = (size_t)s->S * s->q * std::max(Tc, 1L) * MK_N_LEVELS;
   MK_ENTRY_DEVICE(s->device);
   DevBufs scratch;
-  double* dq = scratch.get<double>((size_t)s->S * s->q * std::max(Tc, 1L) * MK_N_LEVELS);
-  if (!dq) return set_err(MK_E_NOMEM, "tile grid scratch");
-  const int rc = session_tile_grids(s, t0, dq, nullptr);
+  double* dq = out_w ? scratch.get<double>(n) : nullptr;
+  double* dqp = out_p ? scratch.get<double>(n) : nullptr;
+  if ((out_w && !dq) || (out_p && !dqp)) return set_err(MK_E_NOMEM, "tile grid scratch");
+  const int rc = session_tile_grids(s, t0, dq, nullptr, dqp);
   if (rc) return rc;
-  HIPCHK(hipMemcpy(out, dq, (size_t)s->S * s->q * Tc * MK_N_LEVELS * 8, hipMemcpyDeviceToHost));
+  const size_t bytes = (size_t)s->S * s->q * Tc * MK_N_LEVELS * 8;
+  if (out_w) HIPCHK(hipMemcpy(out_w, dq, bytes, hipMemcpyDeviceToHost));
+  if (out_p) HIPCHK(hipMemcpy(out_p, dqp, bytes, hipMemcpyDeviceToHost));
   return 0;
+}
+
+extern "C" int mk_session_tile_grids(mk_session* s, int32_t t0, double* out, int32_t device_out) {
+  if (!s || !out) return set_err(MK_E_ARG, "null session/output");
+  return mk_session_tile_grids_wp(s, t0, out, nullptr, device_out);
 }
 
 extern "C" int mk_session_outputs(mk_session* s, mk_outputs* o) {
@@ -925,8 +955,12 @@ extern "C" int mk_session_outputs(mk_session* s, mk_outputs* o) {
   const int S = s->S, P = s->P, q = s->q;
   const int n_test = md.n_test;
   const bool done = s->iter >= md.n_samples;
-  if ((o->parameters || o->w_predict || o->w_pred_samples) && !done)
+  const bool want_p = o->p_predict || o->p_pred_samples || o->p_predict_sum;
+  if ((o->parameters || o->w_predict || o->w_pred_samples || want_p) && !done)
     return set_err(MK_E_ARG, "quantile/predictive outputs need all n.samples iterations");
+  if (want_p && !s->d_xt)
+    return set_err(MK_E_ARG, "p_predict / p_pred_samples / p_predict_sum need x_test (mk_problem.x_test or "
+                             "mk_session_set_test_covars)");
   DevBufs scratch;
   if (o->parameters) {
     double* dq = scratch.get<double>((size_t)S * P * MK_N_LEVELS);
@@ -937,7 +971,33 @@ extern "C" int mk_session_outputs(mk_session* s, mk_outputs* o) {
     // device layout [S][P][200] == R's 200 x P column-major per subset
     HIPCHK(hipMemcpyAsync(o->parameters, dq, (size_t)S * P * MK_N_LEVELS * 8, hipMemcpyDeviceToHost, s->stream));
   }
-  if (s->tiled && (o->w_predict || o->w_pred_samples || o->w_predict_sum)) {
+  if (!s->tiled && (o->p_predict || o->p_predict_sum)) {   // fused: the same draws, transformed on load
+    const int C = q * n_test;
+    double* dq = scratch.get<double>((size_t)S * C * MK_N_LEVELS);
+    if (!dq) return set_err(MK_E_NOMEM, "quantile scratch");
+    int rq = launch_quantiles_prob(S * C, s->stream, md.w_pred, (long)md.n_kept * C, (long)C, md.n_kept, C, s->d_probs,
+                                   MK_N_LEVELS, dq, prob_src(s, 0));
+    if (rq) return rq;
+    if (o->p_predict)
+      HIPCHK(hipMemcpyAsync(o->p_predict, dq, (size_t)S * C * MK_N_LEVELS * 8, hipMemcpyDeviceToHost, s->stream));
+    if (o->p_predict_sum) {
+      double* dsum = scratch.get<double>((size_t)C * MK_N_LEVELS);
+      if (!dsum) return set_err(MK_E_NOMEM, "combine scratch");
+      MK_LAUNCH(k_combine, dim3((unsigned)(((long)C * MK_N_LEVELS + 255) / 256)), dim3(256), 0, s->stream, dq,
+                         S, (long)C * MK_N_LEVELS, dsum, 0);
+      HIPCHK(hipMemcpyAsync(o->p_predict_sum, dsum, (size_t)C * MK_N_LEVELS * 8, hipMemcpyDeviceToHost, s->stream));
+    }
+  }
+  if (!s->tiled && o->p_pred_samples) {   // per subset C x kept column-major == the device's [kept][C]
+    const int C = q * n_test;
+    double* dp = scratch.get<double>((size_t)md.n_kept * C);
+    if (!dp) return set_err(MK_E_NOMEM, "p draw scratch");
+    for (int i = 0; i < S; ++i) {
+      const int rc = pred_prob_to_host(s, i, 0, md.n_kept, C, dp, o->p_pred_samples + (size_t)i * md.n_kept * C, (size_t)C);
+      if (rc) return rc;
+    }
+  }
+  if (s->tiled && (o->w_predict || o->w_pred_samples || o->w_predict_sum || want_p)) {
     HIPCHK(hipStreamSynchronize(s->stream));
     int rc = predict_tiled(s, o);
     if (rc) return rc;

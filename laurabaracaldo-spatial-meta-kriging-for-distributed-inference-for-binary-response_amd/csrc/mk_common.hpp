@@ -98,6 +98,19 @@ __device__ inline double loglik_term(double y, double wt, double eta, int link) 
   return y * eta - wt * softplus(eta);
 }
 
+// Predictive probability p(y = 1) of one kept state at one test row (spPredict's p.y.predictive.samples
+// for the binomial family): eta = x(s)' beta + w(s), the products accumulated by fused multiply-adds
+// in column order j = 0..p-1 from zero, then the link's inverse (k_post_prob's expressions).
+// xrow: the row's first covariate, columns ldx apart.  Every user of p calls this one function, so
+// the quantile grids and the draws agree bit for bit.
+__device__ inline double pred_prob(const double* __restrict__ xrow, long ldx, const double* __restrict__ beta, int p,
+                                   double w, int link) {
+  double acc = 0.0;
+  for (int j = 0; j < p; ++j) acc = fma(xrow[(long)j * ldx], beta[j], acc);
+  const double eta = acc + w;
+  return (link == MK_LINK_PROBIT) ? norm_cdf(eta) : 1.0 / (1.0 + exp(-eta));
+}
+
 // spBayes util logitInv(z, a, b) = b - (b-a)/(1+exp(z))
 __device__ __host__ inline double logit_inv(double z, double a, double b) { return b - (b - a) / (1.0 + exp(z)); }
 __device__ inline double unif_jacobian(double v, double a, double b) { return log(v - a) + log(b - v); }

@@ -15,7 +15,9 @@ int host_error(int code, const char* msg);   // sets mk_last_error()
 int session_info(const mk_session* s, ShardInfo* info);
 int session_param_grids(mk_session* s, double* d_out);                   // [S][P][200]
 int session_wpred_grids(mk_session* s, double* d_out);                   // fused: [S][q n_test][200]
-int session_tile_grids(mk_session* s, int t0, double* d_out, mk_outputs* o);   // tiled: [S][q Tc][200]
+int session_ppred_grids(mk_session* s, double* d_out);                   // fused: [S][q n_test][200] of p
+// tiled: [S][q Tc][200]; d_out_p (optional): the p grids of the same replay
+int session_tile_grids(mk_session* s, int t0, double* d_out, mk_outputs* o, double* d_out_p = nullptr);
 // A plain non-blocking stream of the current device from libmk's stream pool, and its return
 // (drained by the caller): the node driver's per-block streams live as long as the sessions' do.
 hipError_t stream_acquire(int device, hipStream_t* st);

@@ -111,7 +111,56 @@ extern "C" int mk_session_set_test_sites(mk_session* s, int32_t n_test, const do
   if (n_test < 1 || !coords_test) return set_err(MK_E_ARG, "n_test must be >= 1 with coordinates");
   MK_ENTRY_DEVICE(s->device);
   HIPCHK(hipStreamSynchronize(s->stream));
+  int rc = set_test_covars(s, nullptr);   // the covariates belonged to the sites that go
+  if (rc) return rc;
   return kriging_buffers(s, n_test, coords_test);
+}
+
+int mk::set_test_covars(mk_session* s, const double* x_test) {
+  s->release(s->d_xt);
+  s->d_xt = nullptr;
+  if (!x_test) return 0;
+  const size_t n = (size_t)s->q * s->n_test_all * s->p;
+  int rc = s->alloc(&s->d_xt, n);
+  if (rc) return rc;
+  HIPCHK(hipMemcpy(s->d_xt, x_test, n * 8, hipMemcpyHostToDevice));
+  return 0;
+}
+
+extern "C" int mk_session_set_test_covars(mk_session* s, const double* x_test) {
+  if (!s) return set_err(MK_E_ARG, "null session");
+  if (s->n_test_all < 1) return set_err(MK_E_ARG, "x_test needs test sites: the session has none");
+  if (!x_test) return set_err(MK_E_ARG, "null x_test");
+  MK_ENTRY_DEVICE(s->device);
+  HIPCHK(hipStreamSynchronize(s->stream));
+  return set_test_covars(s, x_test);
+}
+
+ProbSrc mk::prob_src(const mk_session* s, int t0) {
+  const Model& md = s->md;
+  ProbSrc ps;
+  ps.samples = md.samples + (long)(md.kept0 + s->win_lo) * md.P;
+  ps.subset_stride = (long)md.n_samples * md.P;
+  ps.row_stride = md.P;
+  ps.x = s->d_xt;
+  ps.ldx = (long)s->q * s->n_test_all;
+  ps.x_off = (long)t0 * s->q;
+  ps.p = md.p;
+  ps.link = md.link;
+  return ps;
+}
+
+int mk::pred_prob_to_host(mk_session* s, int subset, int t0, int n_rows, int n_cols, double* scratch, double* dst,
+                          size_t ld_dst) {
+  ProbSrc ps = prob_src(s, t0);
+  ps.samples += (long)subset * ps.subset_stride;
+  const long n = (long)n_rows * n_cols;
+  MK_LAUNCH(k_pred_prob, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s->stream,
+            s->md.w_pred + (size_t)subset * n_rows * n_cols, (long)n_cols, n_rows, n_cols, scratch, ps);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpy2DAsync(dst, ld_dst * 8, scratch, (size_t)n_cols * 8, (size_t)n_cols * 8, n_rows, hipMemcpyDeviceToHost,
+                          s->stream));
+  return 0;
 }
 
 extern "C" int mk_session_set_kept_window(mk_session* s, int32_t first, int32_t last) {
@@ -125,9 +174,10 @@ extern "C" int mk_session_set_kept_window(mk_session* s, int32_t first, int32_t 
   return 0;
 }
 
-// A tile's draws are in md.w_pred ([S][n_kept][Ct]): its 200-level grids into dq and, if
-// o->w_pred_samples, the draws to the host.  Returns after the stream is idle.
-static int tile_outputs(mk_session* s, int t0, double* dq, mk_outputs* o, int n_kept, int Ct) {
+// A tile's draws are in md.w_pred ([S][n_kept][Ct]): its 200-level grids into dq (and those of
+// p = pred_prob(draw) into dqp) and, if o->w_pred_samples / o->p_pred_samples, the draws to the host.
+// Returns after the stream is idle.
+static int tile_outputs(mk_session* s, int t0, double* dq, double* dqp, mk_outputs* o, int n_kept, int Ct) {
   Model& md = s->md;
   const int S = s->S, q = s->q;
   const long C = (long)q * s->n_test_all;
@@ -136,6 +186,22 @@ static int tile_outputs(mk_session* s, int t0, double* dq, mk_outputs* o, int n_
     const int rq = launch_quantiles(S * Ct, st, md.w_pred, (long)n_kept * Ct, (long)Ct, n_kept, Ct, s->d_probs,
                                     MK_N_LEVELS, dq);
     if (rq) return rq;
+  }
+  const bool p_draws = o && o->p_pred_samples;   // predict_tile checked that the session has x_test
+  if (dqp) {
+    const int rq = launch_quantiles_prob(S * Ct, st, md.w_pred, (long)n_kept * Ct, (long)Ct, n_kept, Ct, s->d_probs,
+                                         MK_N_LEVELS, dqp, prob_src(s, t0));
+    if (rq) return rq;
+  }
+  DevBufs scratch;
+  if (p_draws) {   // one subset at a time through a [n_kept][Ct] scratch
+    double* dp = scratch.get<double>((size_t)n_kept * Ct);
+    if (!dp) return set_err(MK_E_NOMEM, "p draw scratch");
+    for (int i = 0; i < S; ++i) {
+      const int rc = pred_prob_to_host(s, i, t0, n_kept, Ct, dp, o->p_pred_samples + (size_t)i * n_kept * C + (size_t)t0 * q,
+                                       (size_t)C);
+      if (rc) return rc;
+    }
   }
   if (o && o->w_pred_samples)   // per subset (C x kept) column-major
     for (int i = 0; i < S; ++i)
@@ -349,7 +415,7 @@ int mk::krig_tables(mk_session* s) {
 // configs[4]: ~490 X refreshes per subset and tile become 13-21 nodes + 3 checks.  Auto mode
 // (cheb_mode): where the nodes and checks cost fewer exact evaluations than the exact replay's refreshes.
 // Returns 0, MK_CHEB_EXACT (the exact replay must run) or an error (< 0).
-static int predict_tile_cheb(mk_session* s, int t0, double* dq, mk_outputs* o) {
+static int predict_tile_cheb(mk_session* s, int t0, double* dq, mk_outputs* o, double* dqp) {
   Model& md = s->md;
   const int force_n = cheb_mode();
   if (force_n == 0 || s->q != 1 || md.cov_model != MK_COV_EXPONENTIAL) return MK_CHEB_EXACT;
@@ -473,7 +539,7 @@ static int predict_tile_cheb(mk_session* s, int t0, double* dq, mk_outputs* o) {
   c.launches += 1;
   c.flops += (double)evals;
   c.ms = std::fmax(c.ms, emax);
-  return tile_outputs(s, t0, dq, o, n_kept, s->q * Tc);
+  return tile_outputs(s, t0, dq, dqp, o, n_kept, s->q * Tc);
 }
 
 // spPredict after the fit (MK.R:87-89) over test-site tiles: replays the kriging of every kept
@@ -483,10 +549,11 @@ static int predict_tile_cheb(mk_session* s, int t0, double* dq, mk_outputs* o) {
 // their sum are bit-identical to the fused path.  Per tile the device holds q*T x kept draws
 // per subset instead of q*n_test x kept.
 // One tile [t0, t0 + Tc): the replay, then the tile's 200-level grids into dq ([S][q*Tc][200] in
-// HBM, on s->stream) and, if o->w_pred_samples, its draws to the host.  Returns after the stream
-// is idle.
-int mk::predict_tile(mk_session* s, int t0, double* dq, mk_outputs* o) {
-  const int rc_cheb = predict_tile_cheb(s, t0, dq, o);
+// HBM, on s->stream; dqp: those of the predictive probabilities, from the same draws) and, if
+// o->w_pred_samples / o->p_pred_samples, its draws to the host.  Returns after the stream is idle.
+int mk::predict_tile(mk_session* s, int t0, double* dq, mk_outputs* o, double* dqp) {
+  if ((dqp || (o && o->p_pred_samples)) && !s->d_xt) return set_err(MK_E_ARG, "predictive probabilities need x_test");
+  const int rc_cheb = predict_tile_cheb(s, t0, dq, o, dqp);
   if (rc_cheb != MK_CHEB_EXACT) return rc_cheb;
   Model& md = s->md;
   const int S = s->S, q = s->q;
@@ -548,7 +615,7 @@ int mk::predict_tile(mk_session* s, int t0, double* dq, mk_outputs* o) {
               (const int*)nullptr, s->d_run_start, n_kept);
     HIPCHK(hipGetLastError());
   }
-  return tile_outputs(s, t0, dq, o, n_kept, Ct);
+  return tile_outputs(s, t0, dq, dqp, o, n_kept, Ct);
 }
 
 int mk::predict_tiled(mk_session* s, mk_outputs* o) {
@@ -561,10 +628,22 @@ int mk::predict_tiled(mk_session* s, mk_outputs* o) {
   double* dsum = scratch.get<double>((size_t)q * T * MK_N_LEVELS);
   if (!dq || !dsum) return set_err(MK_E_NOMEM, "tiled kriging scratch");
   const bool grids = o->w_predict || o->w_predict_sum;
+  const bool pgrids = o->p_predict || o->p_predict_sum;
+  double* dqp = pgrids ? scratch.get<double>((size_t)S * q * T * MK_N_LEVELS) : nullptr;
+  if (pgrids && !dqp) return set_err(MK_E_NOMEM, "tiled kriging scratch");
   for (int t0 = 0; t0 < n_test; t0 += T) {
     const int Ct = q * std::min(T, n_test - t0);
-    int rc = predict_tile(s, t0, grids ? dq : nullptr, o);
+    int rc = predict_tile(s, t0, grids ? dq : nullptr, o, dqp);
     if (rc) return rc;
+    if (o->p_predict)
+      HIPCHK(hipMemcpy2DAsync(o->p_predict + (size_t)t0 * q * MK_N_LEVELS, (size_t)C * MK_N_LEVELS * 8, dqp,
+                              (size_t)Ct * MK_N_LEVELS * 8, (size_t)Ct * MK_N_LEVELS * 8, S, hipMemcpyDeviceToHost, st));
+    if (o->p_predict_sum) {
+      MK_LAUNCH(k_combine, dim3((unsigned)(((long)Ct * MK_N_LEVELS + 255) / 256)), dim3(256), 0, st, dqp, S,
+                         (long)Ct * MK_N_LEVELS, dsum, 0);
+      HIPCHK(hipMemcpyAsync(o->p_predict_sum + (size_t)t0 * q * MK_N_LEVELS, dsum, (size_t)Ct * MK_N_LEVELS * 8,
+                            hipMemcpyDeviceToHost, st));
+    }
     if (o->w_predict)   // per subset [C][200]: this tile's columns
       HIPCHK(hipMemcpy2DAsync(o->w_predict + (size_t)t0 * q * MK_N_LEVELS, (size_t)C * MK_N_LEVELS * 8, dq,
                               (size_t)Ct * MK_N_LEVELS * 8, (size_t)Ct * MK_N_LEVELS * 8, S, hipMemcpyDeviceToHost, st));

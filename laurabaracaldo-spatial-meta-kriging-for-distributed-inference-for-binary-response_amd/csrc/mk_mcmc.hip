@@ -1579,17 +1579,19 @@ __global__ __launch_bounds__(256) void k_run_start(const int* __restrict__ plist
 // ---------------------------------------------------------------- 8. type-7 quantiles (MK.R:88-89)
 // One workgroup per (subset, column): bitonic sort of the kept values in LDS (dynamic: the next
 // power of two >= n_rows doubles, at most MK_QUANT_MAX = 128 KB), then R's quantile.default type 7:
-// (1-h) x[lo] + h x[hi] (no FMA contraction).
-__global__ __launch_bounds__(256) void k_quantiles(const double* __restrict__ data, long subset_stride, long row_stride,
-                                                   int n_rows, int n_cols, const double* __restrict__ probs, int n_probs,
-                                                   double* __restrict__ out /* [S][n_cols][n_probs] */) {
-  extern __shared__ double v[];
-  const int s = blockIdx.x / n_cols, c = blockIdx.x % n_cols;
-  const double* src = data + (long)s * subset_stride + c;
+// (1-h) x[lo] + h x[hi] (no FMA contraction).  k_quantiles sorts the values as stored;
+// k_quantiles_prob sorts pred_prob of them (the transform is applied as LDS is filled, so the
+// probabilities of a [S][kept][C] draw buffer never exist in memory).
+__device__ inline int quant_pow2(int n_rows) {
   int n2 = 1;
   while (n2 < n_rows) n2 <<= 1;
-  for (int r = threadIdx.x; r < n2; r += 256) v[r] = (r < n_rows) ? src[(long)r * row_stride] : INFINITY;
-  __syncthreads();
+  return n2;
+}
+
+// v[0 .. n2) filled (padding +INFINITY) and a barrier passed: sorts ascending, then writes the
+// n_probs type-7 quantiles of the first n_rows values to o.  256 threads.
+__device__ inline void quant_sort_readout(double* v, int n2, int n_rows, const double* __restrict__ probs, int n_probs,
+                                          double* __restrict__ o) {
   for (int size = 2; size <= n2; size <<= 1) {
     for (int stride = size >> 1; stride > 0; stride >>= 1) {
       for (int t = threadIdx.x; t < n2 / 2; t += 256) {
@@ -1602,7 +1604,6 @@ __global__ __launch_bounds__(256) void k_quantiles(const double* __restrict__ da
       __syncthreads();
     }
   }
-  double* o = out + ((long)s * n_cols + c) * n_probs;
   for (int l = threadIdx.x; l < n_probs; l += 256) {
     const double index = 1.0 + (double)(n_rows - 1) * probs[l];
     const double flo = floor(index), fhi = ceil(index);
@@ -1611,6 +1612,51 @@ __global__ __launch_bounds__(256) void k_quantiles(const double* __restrict__ da
     const double hh = index - flo;
     o[l] = (index > flo && qhi != qlo) ? (1.0 - hh) * qlo + hh * qhi : qlo;
   }
+}
+
+__global__ __launch_bounds__(256) void k_quantiles(const double* __restrict__ data, long subset_stride, long row_stride,
+                                                   int n_rows, int n_cols, const double* __restrict__ probs, int n_probs,
+                                                   double* __restrict__ out /* [S][n_cols][n_probs] */) {
+  extern __shared__ double v[];
+  const int s = blockIdx.x / n_cols, c = blockIdx.x % n_cols;
+  const double* src = data + (long)s * subset_stride + c;
+  const int n2 = quant_pow2(n_rows);
+  for (int r = threadIdx.x; r < n2; r += 256) v[r] = (r < n_rows) ? src[(long)r * row_stride] : INFINITY;
+  __syncthreads();
+  quant_sort_readout(v, n2, n_rows, probs, n_probs, out + ((long)s * n_cols + c) * n_probs);
+}
+
+// The same summary of p = pred_prob(draw) (obj[[i]]$p.predict): data is the kriging draw buffer as
+// k_quantiles takes it, row r of subset s being the draw of the window's r-th kept state, whose beta
+// ps locates in the recorded samples; column c is row ps.x_off + c of x_test.  Padding rows
+// (r >= n_rows) are +INFINITY and read nothing.
+__global__ __launch_bounds__(256) void k_quantiles_prob(const double* __restrict__ data, long subset_stride,
+                                                        long row_stride, int n_rows, int n_cols,
+                                                        const double* __restrict__ probs, int n_probs,
+                                                        double* __restrict__ out /* [S][n_cols][n_probs] */, ProbSrc ps) {
+  extern __shared__ double v[];
+  const int s = blockIdx.x / n_cols, c = blockIdx.x % n_cols;
+  const double* src = data + (long)s * subset_stride + c;
+  const double* beta = ps.samples + (long)s * ps.subset_stride;
+  const double* xrow = ps.x + ps.x_off + c;
+  const int n2 = quant_pow2(n_rows);
+  for (int r = threadIdx.x; r < n2; r += 256)
+    v[r] = (r < n_rows) ? pred_prob(xrow, ps.ldx, beta + (long)r * ps.row_stride, ps.p, src[(long)r * row_stride], ps.link)
+                        : INFINITY;
+  __syncthreads();
+  quant_sort_readout(v, n2, n_rows, probs, n_probs, out + ((long)s * n_cols + c) * n_probs);
+}
+
+// p = pred_prob of one subset's draws, elementwise: w and out are [n_rows][n_cols] (rows row_stride
+// apart in w, n_cols apart in out), ps.samples already at this subset's first window row.  For the
+// host copy of the p draws only (p.y.predictive.samples); the grids never go through memory.
+__global__ __launch_bounds__(256) void k_pred_prob(const double* __restrict__ w, long row_stride, int n_rows, int n_cols,
+                                                   double* __restrict__ out, ProbSrc ps) {
+  const long e = (long)blockIdx.x * 256 + threadIdx.x;
+  if (e >= (long)n_rows * n_cols) return;
+  const int r = (int)(e / n_cols), c = (int)(e % n_cols);
+  out[e] = pred_prob(ps.x + ps.x_off + c, ps.ldx, ps.samples + (long)r * ps.row_stride, ps.p, w[(long)r * row_stride + c],
+                     ps.link);
 }
 
 // ---------------------------------------------------------------- 9. combine (MK.R:123-133)

@@ -219,7 +219,7 @@ struct Block {
   mk_session* ses = nullptr;
   hipStream_t st = nullptr;
   hipEvent_t packed = nullptr;
-  DBuf grids, send, recv, comb, sum, iters;   // iters: Weiszfeld iteration counts (as int)
+  DBuf grids, grids_p, send, recv, comb, sum, iters;   // grids_p: a tile's p grids; iters: Weiszfeld iteration counts (as int)
   ~Block() {
     (void)hipSetDevice(dev);
     if (st) (void)hipStreamSynchronize(st);
@@ -269,10 +269,11 @@ std::string rccl_detail(ncclResult_t e) {
 
 constexpr int L = MK_N_LEVELS;
 
-// The exchange + combine of one grid set: every block's grids [S_r][C][200] are in b.grids.
-// Writes (when not NULL) the combined columns: mean (or median) -> h_comb, sum -> h_sum, both
-// 200 x C column-major with column c at c*200.
-int exchange_combine(Node& nd, long C, const mk_combined* comb, double* h_comb, double* h_sum) {
+// The exchange + combine of one grid set: every block's grids [S_r][C][200] are in b.grids (or the
+// buffer `src` names).  Writes (when not NULL) the combined columns: mean (or median) -> h_comb,
+// sum -> h_sum, both 200 x C column-major with column c at c*200.
+int exchange_combine(Node& nd, long C, const mk_combined* comb, double* h_comb, double* h_sum,
+                     DBuf Block::*src = &Block::grids) {
   if (!h_comb && !h_sum) return 0;
   const int G = nd.G, K = nd.K;
   const long per = std::max(1L, (C + G - 1) / G);
@@ -292,7 +293,7 @@ int exchange_combine(Node& nd, long C, const mk_combined* comb, double* h_comb, 
       MHIP(hipMemsetAsync(x.send.p, 0, (size_t)G * x.S * per * L * 8, x.st));
       for (int j = 0; j < G; ++j)
         if (ncol(j) > 0)
-          MHIP(hipMemcpy2DAsync(x.send.p + (size_t)j * x.S * per * L, (size_t)per * L * 8, x.grids.p + col0(j) * L,
+          MHIP(hipMemcpy2DAsync(x.send.p + (size_t)j * x.S * per * L, (size_t)per * L * 8, (x.*src).p + col0(j) * L,
                                 (size_t)C * L * 8, (size_t)ncol(j) * L * 8, x.S, hipMemcpyDeviceToDevice, x.st));
     }
     MHIP(hipEventRecord(x.packed, x.st));
@@ -386,6 +387,8 @@ extern "C" int mk_meta_fit(const mk_problem* pr, const mk_config* c, const int32
     if (devices[r] < 0 || devices[r] >= ndev) return fail(MK_E_ARG, "bad device ordinal in the device list");
   for (int i = 0; i < K; ++i)
     if (pr->n_part[i] < 1) return fail(MK_E_ARG, "every subset needs >= 1 site");
+  const bool want_p = (out && (out->p_predict || out->p_pred_samples || out->p_predict_sum)) || (comb && comb->result3);
+  if (want_p && !pr->x_test) return fail(MK_E_ARG, "p_predict / p_pred_samples / p_predict_sum / result3 need x_test");
   const int q = pr->q, p = pr->p, n_samples = c->n_batch * c->batch_length;
   if (c->n_batch < 1 || c->batch_length < 1) return fail(MK_E_ARG, "n.batch and batch.length must be >= 1");
 
@@ -408,7 +411,7 @@ extern "C" int mk_meta_fit(const mk_problem* pr, const mk_config* c, const int32
     x->dev = devices[r];
     x->lo = (int)(((long)r * K) / G);
     x->S = (int)(((long)(r + 1) * K) / G) - x->lo;
-    x->grids.dev = x->send.dev = x->recv.dev = x->comb.dev = x->sum.dev = x->iters.dev = x->dev;
+    x->grids.dev = x->grids_p.dev = x->send.dev = x->recv.dev = x->comb.dev = x->sum.dev = x->iters.dev = x->dev;
     nd.b.push_back(std::move(x));
   }
   int rc = nd.pool->run([&](int r) -> int {
@@ -487,6 +490,7 @@ extern "C" int mk_meta_fit(const mk_problem* pr, const mk_config* c, const int32
     if (out->samples) o.samples = out->samples + (size_t)x.lo * n_samples * P;
     if (out->w_samples) o.w_samples = out->w_samples + (size_t)s0 * q * n_samples;
     if (out->w_pred_samples) o.w_pred_samples = out->w_pred_samples + (size_t)x.lo * C * n_kept;
+    if (out->p_pred_samples) o.p_pred_samples = out->p_pred_samples + (size_t)x.lo * C * n_kept;
     if (out->acceptance) o.acceptance = out->acceptance + (size_t)x.lo * c->n_batch * (p + n_theta + 1);
     return o;
   };
@@ -494,8 +498,8 @@ extern "C" int mk_meta_fit(const mk_problem* pr, const mk_config* c, const int32
     Block& x = *nd.b[r];
     if (!x.ses) return 0;
     mk_outputs o = shard_out(x);
-    if (tiled) o.w_pred_samples = nullptr;   // written per tile below
-    if (!o.samples && !o.w_samples && !o.w_pred_samples && !o.acceptance) return 0;
+    if (tiled) o.w_pred_samples = o.p_pred_samples = nullptr;   // written per tile below
+    if (!o.samples && !o.w_samples && !o.w_pred_samples && !o.p_pred_samples && !o.acceptance) return 0;
     return mk_session_outputs(x.ses, &o);
   });
   if (rc) return rc;
@@ -522,7 +526,24 @@ extern "C" int mk_meta_fit(const mk_problem* pr, const mk_config* c, const int32
     double* h_w = out ? out->w_predict : nullptr;
     double* h_sum = out ? out->w_predict_sum : nullptr;
     double* h_comb = comb ? comb->result2 : nullptr;
-    const bool want_w = h_w || h_sum || h_comb || (tiled && out && out->w_pred_samples);
+    // p.predict grids -> out->p_predict; combine -> comb->result3 and the sum -> out->p_predict_sum
+    double* h_p = out ? out->p_predict : nullptr;
+    double* h_psum = out ? out->p_predict_sum : nullptr;
+    double* h_pcomb = comb ? comb->result3 : nullptr;
+    const bool want_pg = h_p || h_psum || h_pcomb;
+    const bool want_w = h_w || h_sum || h_comb || (tiled && (want_pg || (out && (out->w_pred_samples || out->p_pred_samples))));
+    if (want_pg && !tiled) {
+      rc = nd.pool->run([&](int r) -> int {
+        Block& x = *nd.b[r];
+        if (!x.ses) return 0;
+        int e = x.grids.ensure((size_t)x.S * C * L);
+        if (e || (e = session_ppred_grids(x.ses, x.grids.p))) return e;
+        if (h_p) MHIP(hipMemcpy(h_p + (size_t)x.lo * C * L, x.grids.p, (size_t)x.S * C * L * 8, hipMemcpyDeviceToHost));
+        return 0;
+      });
+      if (rc) return rc;
+      if ((rc = exchange_combine(nd, C, comb, h_pcomb, h_psum))) return rc;
+    }
     if (want_w && !tiled) {
       rc = nd.pool->run([&](int r) -> int {
         Block& x = *nd.b[r];
@@ -554,7 +575,11 @@ extern "C" int mk_meta_fit(const mk_problem* pr, const mk_config* c, const int32
           if (!x.ses) return 0;
           mk_outputs o = shard_out(x);
           int e = x.grids.ensure((size_t)x.S * Ct * L);
-          if (e || (e = session_tile_grids(x.ses, t0, x.grids.p, &o))) return e;
+          if (!e && want_pg) e = x.grids_p.ensure((size_t)x.S * Ct * L);
+          if (e || (e = session_tile_grids(x.ses, t0, x.grids.p, &o, want_pg ? x.grids_p.p : nullptr))) return e;
+          if (h_p)
+            MHIP(hipMemcpy2D(h_p + (size_t)x.lo * C * L + (size_t)t0 * q * L, (size_t)C * L * 8, x.grids_p.p,
+                             (size_t)Ct * L * 8, (size_t)Ct * L * 8, x.S, hipMemcpyDeviceToHost));
           if (h_w)   // per subset [C][200]: this tile's columns
             MHIP(hipMemcpy2D(h_w + (size_t)x.lo * C * L + (size_t)t0 * q * L, (size_t)C * L * 8, x.grids.p,
                              (size_t)Ct * L * 8, (size_t)Ct * L * 8, x.S, hipMemcpyDeviceToHost));
@@ -563,6 +588,9 @@ extern "C" int mk_meta_fit(const mk_problem* pr, const mk_config* c, const int32
         if (rc) return rc;
         if ((rc = exchange_combine(nd, Ct, comb, h_comb ? h_comb + (size_t)t0 * q * L : nullptr,
                                    h_sum ? h_sum + (size_t)t0 * q * L : nullptr)))
+          return rc;
+        if (want_pg && (rc = exchange_combine(nd, Ct, comb, h_pcomb ? h_pcomb + (size_t)t0 * q * L : nullptr,
+                                              h_psum ? h_psum + (size_t)t0 * q * L : nullptr, &Block::grids_p)))
           return rc;
       }
     }

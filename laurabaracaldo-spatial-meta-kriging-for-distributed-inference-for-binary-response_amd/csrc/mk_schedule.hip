@@ -85,6 +85,21 @@ int mk::launch_quantiles(unsigned grid, hipStream_t st, const double* data, long
   return 0;
 }
 
+// The same summary of the predictive probabilities of a kriging draw buffer (k_quantiles_prob): data
+// and the shape arguments as launch_quantiles takes them, ps as prob_src makes it.
+int mk::launch_quantiles_prob(unsigned grid, hipStream_t st, const double* data, long subset_stride, long row_stride,
+                              int n_rows, int n_cols, const double* probs, int n_probs, double* out, const ProbSrc& ps) {
+  HIPCHK(hipFuncSetAttribute((const void*)k_quantiles_prob, hipFuncAttributeMaxDynamicSharedMemorySize, MK_QUANT_MAX * 8));
+  if (n_rows < 1 || n_rows > MK_QUANT_MAX)
+    return set_err(MK_E_ARG, "quantile summaries take 1 .. " + std::to_string(MK_QUANT_MAX) + " kept samples");
+  size_t n2 = 1;
+  while (n2 < (size_t)n_rows) n2 <<= 1;
+  MK_LAUNCH(k_quantiles_prob, dim3(grid), dim3(256), n2 * 8, st, data, subset_stride, row_stride, n_rows, n_cols,
+                     probs, n_probs, out, ps);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
 // Tile shape of a GEMM launch: 64-sub-tiles (bit-identical, mk_gemm.hpp) when the 128-tile grid
 // would leave the chip short of work -- fewer than 256 workgroups (one per CU; 512 before the
 // lookahead schedule, whose concurrent chain fills the rest: 32 subsets 6,360 -> 6,546

@@ -232,6 +232,7 @@ struct mk_session {
   std::vector<void*> kbufs;       // the kriging buffers (re-sized by mk_session_set_test_sites)
   std::vector<double> bbox;       // [S][4] xmin xmax ymin ymax of each subset's sites (Matern table ranges)
   double* d_ct_all = nullptr;     // all test sites [2][n_test_pad_all] (tiled mode)
+  double* d_xt = nullptr;         // x_test of the current test sites, (q n_test_all) x p column-major (NULL: none)
   int* d_slist = nullptr;         // tiled replay: per-outcome subset lists [q][S] + counts [q]
   int* d_run_start = nullptr;     // tiled replay, q = 1: first window state of each subset's pending draws
   int* d_scount = nullptr;
@@ -312,6 +313,8 @@ void drain_timers(mk_session* s);
 bool set_gemm_lds();
 int launch_quantiles(unsigned grid, hipStream_t st, const double* data, long subset_stride, long row_stride,
                      int n_rows, int n_cols, const double* probs, int n_probs, double* out);
+int launch_quantiles_prob(unsigned grid, hipStream_t st, const double* data, long subset_stride, long row_stride,
+                          int n_rows, int n_cols, const double* probs, int n_probs, double* out, const ProbSrc& ps);
 void launch_candidates(const Model& md, const MatSet& ms, hipStream_t st, int n_entries, int h0, int hc, int which,
                        int iter, const int* slist = nullptr, const int* scount = nullptr);
 void launch_cholesky(mk_session* s, Group& g, int h0, int hc, const int* slist = nullptr, const int* scount = nullptr,
@@ -325,7 +328,15 @@ void run_iteration(mk_session* s, int it);
 // ---- mk_krig.hip
 int kriging_buffers(mk_session* s, int n_test_all, const double* coords_test);
 int krig_tables(mk_session* s);
-int predict_tile(mk_session* s, int t0, double* dq, mk_outputs* o);
+int predict_tile(mk_session* s, int t0, double* dq, mk_outputs* o, double* dqp = nullptr);
 int predict_tiled(mk_session* s, mk_outputs* o);
+// x_test (C x p column-major, C = q n_test_all; NULL drops it) of the current test sites into HBM
+int set_test_covars(mk_session* s, const double* x_test);
+// pred_prob's inputs for the draws in md.w_pred: the window's first kept state, test row t0 * q first
+ProbSrc prob_src(const mk_session* s, int t0);
+// One subset's p draws to the host: k_pred_prob of its [n_rows][n_cols] block of md.w_pred into
+// scratch (n_rows * n_cols doubles), then rows ld_dst apart at dst (stream-ordered, not waited for)
+int pred_prob_to_host(mk_session* s, int subset, int t0, int n_rows, int n_cols, double* scratch, double* dst,
+                      size_t ld_dst);
 
 }  // namespace mk

@@ -119,6 +119,19 @@ struct ChebK {
   long T_pad;
 };
 
+// What turns a kriging draw w(s) into the predictive probability p(y = 1) (pred_prob): beta of the
+// draw's kept state and the test row's covariates.  Draw (subset s, window row r, column c) reads
+// beta at samples + s*subset_stride + r*row_stride and covariate j at x[x_off + c + j*ldx].
+struct ProbSrc {
+  const double* samples;   // subset 0's recorded row of the window's first kept state (beta = its first p columns)
+  long subset_stride;      // n_samples * P
+  long row_stride;         // P
+  const double* x;         // x_test on the device, (q n_test_all) x p column-major
+  long ldx;                // q * n_test_all
+  long x_off;              // the first column's row of x (a tile's t0 * q; 0 when fused)
+  int p, link;
+};
+
 __device__ inline long mat_elems(const MatSet& m) { return (long)m.ld * m.ld; }
 __device__ inline double* mat_slot(const MatSet& m, int sh, int slot) {
   return m.L + ((long)sh * 2 + slot) * mat_elems(m);

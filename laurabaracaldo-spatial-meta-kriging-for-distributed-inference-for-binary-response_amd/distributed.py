@@ -186,13 +186,17 @@ def combine_tiles(tile_grids, n_test, tile, q, K, dist, method="mean", device=No
     return out
 
 
-def meta_fit_distributed(y, x, weight, coords, q, index_part, coords_test, cfg, dist, device=0, method="mean"):
+def meta_fit_distributed(y, x, weight, coords, q, index_part, coords_test, cfg, dist, device=0, method="mean",
+                         x_test=None):
     """Fit this rank's shard of subsets on its GPU, then the one exchange: the column-sharded
     combine (MK.R:119-133; method="median" for the Weiszfeld extension).
 
     Returns (obj_local, result, result2): the local `obj` entries (MK.R:108) and the
     combined grids (MK.R:127, MK.R:133), identical on every rank.  A rank whose shard is
-    empty (K < world) fits nothing and still takes part in the exchange."""
+    empty (K < world) fits nothing and still takes part in the exchange.
+    With x_test (the test sites' covariates, the same on every rank) the local entries also hold
+    'p.predict' and the return value is (obj_local, result, result2, result3): the subsets' grids of
+    p(y = 1) combined through the same exchange as result2."""
     from .metakriging import meta_fit
     import torch
     K = len(index_part)
@@ -200,7 +204,7 @@ def meta_fit_distributed(y, x, weight, coords, q, index_part, coords_test, cfg, 
     obj = []
     if hi > lo:
         obj = meta_fit(y, x, weight, coords, q, index_part[lo:hi], coords_test=coords_test, cfg=cfg, subset_base=lo,
-                       device=device)
+                       device=device, x_test=x_test)
     dev = torch.device("cuda", device) if dist.get_backend() == "nccl" else None
     P = cfg.P
     par = np.stack([o["parameters"] for o in obj]) if obj else np.zeros((0, 200, P))
@@ -210,4 +214,7 @@ def meta_fit_distributed(y, x, weight, coords, q, index_part, coords_test, cfg, 
         C = q * np.asarray(coords_test).shape[0]
         wp = np.stack([o["w.predict"] for o in obj]) if obj else np.zeros((0, 200, C))
         result2 = combine_sharded(wp, K, dist, method=method, device=dev, gpu=device)
+        if x_test is not None:
+            pp = np.stack([o["p.predict"] for o in obj]) if obj else np.zeros((0, 200, C))
+            return obj, result, result2, combine_sharded(pp, K, dist, method=method, device=dev, gpu=device)
     return obj, result, result2

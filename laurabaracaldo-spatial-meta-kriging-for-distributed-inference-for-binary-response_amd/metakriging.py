@@ -89,16 +89,17 @@ def r_sample_replace(n, size, seed):
 
 
 def meta_fit(y, x, weight, coords, q, index_part, coords_test=None, cfg=None, subset_base=0, device=0,
-             cov_model="exponential", n_batch=100, batch_length=50, seed=20250114):
+             cov_model="exponential", n_batch=100, batch_length=50, seed=20250114, x_test=None):
     """All subsets of one shard on one GPU; returns the list `obj` of MK.R:108 for those subsets:
-    [{'parameters': 200 x P, 'w.predict': 200 x (q n_test)}, ...]."""
+    [{'parameters': 200 x P, 'w.predict': 200 x (q n_test)}, ...]; with x_test (MK.R:87's x.test) each
+    also holds 'p.predict' (200 x (q n_test)): the grid of p(y = 1) at the test sites."""
     p = np.asarray(x).shape[1]
     if cfg is None:
         beta0, bt = start_values(y, x, weight, q)
         cfg = default_config(q, p, beta0, bt, cov_model=cov_model, n_batch=n_batch, batch_length=batch_length,
                              seed=seed)
     subsets = [subset_data(y, x, weight, coords, q, idx) for idx in index_part]
-    with Session(subsets, cfg, coords_test=coords_test, subset_base=subset_base, device=device) as ses:
+    with Session(subsets, cfg, coords_test=coords_test, subset_base=subset_base, device=device, x_test=x_test) as ses:
         ses.run(cfg.n_samples)
         out = ses.outputs()
     res = []
@@ -106,20 +107,25 @@ def meta_fit(y, x, weight, coords, q, index_part, coords_test=None, cfg=None, su
         d = {"parameters": out["parameters"][i]}
         if "w_predict" in out:
             d["w.predict"] = out["w_predict"][i]
+        if "p_predict" in out:
+            d["p.predict"] = out["p_predict"][i]
         res.append(d)
     return res
 
 
 def partitioned_spMvGLM(i, y, x, weight, n, q, n_part, coords_test, x_test, index_part, coords,
                         cov_model="exponential", n_batch=100, batch_length=50, seed=20250114, device=0):
-    """MK.R:46-96 for subset i (1-based, as the reference): list(parameters, w.predict)."""
+    """MK.R:46-96 for subset i (1-based, as the reference): list(parameters, w.predict), and p.predict
+    when x_test (the argument MK.R:87 hands spPredict) is given."""
     return meta_fit(y, x, weight, coords, q, [index_part[i - 1]], coords_test=coords_test, subset_base=i - 1,
-                    device=device, cov_model=cov_model, n_batch=n_batch, batch_length=batch_length, seed=seed)[0]
+                    device=device, cov_model=cov_model, n_batch=n_batch, batch_length=batch_length, seed=seed,
+                    x_test=x_test)[0]
 
 
 def combine_results(obj, device=0, method="mean"):
     """MK.R:123-133: result (200 x P) and result2 (200 x q n_test).  method="median" is the
-    Weiszfeld geometric-median extension (the reference averages)."""
+    Weiszfeld geometric-median extension (the reference averages).
+    combine_predictive(obj) gives result3 from the subsets' p.predict grids the same way."""
     if method == "mean":
         comb = lambda grids: combine(grids, device=device)             # noqa: E731
     elif method == "median":
@@ -129,6 +135,18 @@ def combine_results(obj, device=0, method="mean"):
     result = comb([o["parameters"] for o in obj])
     result2 = comb([o["w.predict"] for o in obj]) if "w.predict" in obj[0] else None
     return result, result2
+
+
+def combine_predictive(obj, device=0, method="mean"):
+    """result3 (200 x q n_test): the subsets' p.predict grids combined as combine_results combines
+    w.predict; None when the subsets were fitted without x_test."""
+    if "p.predict" not in obj[0]:
+        return None
+    if method == "mean":
+        return combine([o["p.predict"] for o in obj], device=device)
+    if method == "median":
+        return combine_median([o["p.predict"] for o in obj], device=device)[0]
+    raise ValueError(f"error: unknown combine method '{method}'")
 
 
 def posterior_summary(result, result2, x_test, q=None, samplesize=1000, seed=20250114, device=0, rng="philox",
@@ -143,7 +161,8 @@ def posterior_summary(result, result2, x_test, q=None, samplesize=1000, seed=202
 
 
 def reference_flow(d, K, q, cov_model="exponential", n_batch=100, batch_length=50, seed=20250114, devices=(0,),
-                   method="mean", predict_tile=0, partition_method="R", samplesize=1000, progress=None):
+                   method="mean", predict_tile=0, partition_method="R", samplesize=1000, progress=None,
+                   predictive=False):
     """The reference script end to end in one process over the GPUs in `devices` (mk_meta_fit: the
     subsets sharded over them in-library, the combine device to device):
 
@@ -155,7 +174,9 @@ def reference_flow(d, K, q, cov_model="exponential", n_batch=100, batch_length=5
       resample, p(y=1), quant.  MK.R:136-165  posterior_summary
 
     d: synthetic.generate output.  progress(iterations, n_samples) is called between amcmc batches
-    (return True to stop).  Returns (phases, result, result2, summary, cfg) -- phases in seconds of
+    (return True to stop).  predictive=True hands d["x_test"] to the fit as MK.R:87's x.test: every
+    subset's grids of p(y = 1) at the test sites are made and combined too, summary["result3"].
+    Returns (phases, result, result2, summary, cfg) -- phases in seconds of
     wall clock: set-up (partition, glm, subset slicing), the chains (to the last batch boundary),
     quantiles + combine, post-processing, and the whole."""
     import time
@@ -179,7 +200,7 @@ def reference_flow(d, K, q, cov_model="exponential", n_batch=100, batch_length=5
         return bool(progress(it, n_samples)) if progress is not None else False
 
     fit = meta_fit_node(subs, cfg, coords_test=d["coords_test"], devices=devices, method=method, per_subset=False,
-                        progress=_progress)                                                  # MK.R:100-133
+                        progress=_progress, x_test=d["x_test"] if predictive else None)    # MK.R:100-133
     t3 = time.perf_counter()
     t["chains_s"] = stamp.get("chains", t3) - t1
     t["quantiles_combine_s"] = t3 - stamp.get("chains", t3)
@@ -187,6 +208,8 @@ def reference_flow(d, K, q, cov_model="exponential", n_batch=100, batch_length=5
     summ = posterior_summary(fit["result"], fit["result2"], d["x_test"], samplesize=samplesize, seed=seed,
                              device=int(devices[0]))                                         # MK.R:136-165
     t["post_s"] = time.perf_counter() - t2
+    if "result3" in fit:
+        summ["result3"] = fit["result3"]
     t["end_to_end_s"] = time.perf_counter() - t0
     t["exchange"] = fit["exchange"]          # the combine's all-to-all: "rccl" (distinct GPUs) or "copy"
     t["comm_ranks"] = fit["comm_ranks"]      # ranks RCCL's communicators hold (copies: device blocks)

@@ -22,17 +22,21 @@ N_LEVELS = _lib.N_LEVELS
 
 def meta_fit_node(subsets, cfg, coords_test=None, devices=(0,), subset_base=0, method="mean", per_subset=True,
                   samples=False, w_samples=False, w_pred_samples=False, acceptance=False, w_predict_sum=False,
-                  progress=None, record_w=False, max_iter=100, tol=1e-12):
+                  progress=None, record_w=False, max_iter=100, tol=1e-12, x_test=None, p_pred_samples=False,
+                  p_predict_sum=False):
     """Fit all subsets over `devices` and combine.  Returns a dict with 'result' (200 x P, MK.R:127),
     'result2' (200 x q n_test, MK.R:133; None without test sites), 'exchange' ('rccl' / 'copy'),
     'comm_ranks' (the ranks the exchange spans: RCCL's own ncclCommCount, or the blocks for copies),
     and per subset (lists, as Session.outputs lays them out) 'parameters' / 'w_predict' when
     per_subset, plus the optional 'samples', 'w_samples', 'w_pred_samples', 'acceptance',
-    'w_predict_sum' (the sequential sum of all K w.predict grids)."""
+    'w_predict_sum' (the sequential sum of all K w.predict grids).  With x_test ((q n_test) x p, the
+    test sites' covariates) also 'result3' (200 x q n_test: the subsets' grids of p(y = 1) =
+    linkinv(x.test beta + w) combined as result2 is), per subset 'p_predict', and the optional
+    'p_pred_samples' / 'p_predict_sum'."""
     lib = _lib.load()
     if method not in ("mean", "median"):
         raise ValueError(f"error: unknown combine method '{method}'")
-    pp = PackedProblem(subsets, cfg, coords_test, subset_base)
+    pp = PackedProblem(subsets, cfg, coords_test, subset_base, x_test=x_test)
     c, keep = cfg.to_c(device=0, record_w=record_w or w_samples)
     devs = np.ascontiguousarray(devices, dtype=np.int32)
     K, P, q, n_test = pp.S, cfg.P, cfg.q, pp.n_test
@@ -60,11 +64,25 @@ def meta_fit_node(subsets, cfg, coords_test=None, devices=(0,), subset_base=0, m
     if w_predict_sum and n_test:
         res["w_predict_sum"] = np.zeros((C, N_LEVELS))
         o.w_predict_sum = _lib.dptr(res["w_predict_sum"])
+    have_x = pp.x_test is not None and n_test > 0
+    if (p_pred_samples or p_predict_sum) and not have_x:
+        raise ValueError("error: p_pred_samples / p_predict_sum need x_test")
+    if have_x and per_subset:
+        res["p_predict"] = np.zeros((K, C, N_LEVELS))
+        o.p_predict = _lib.dptr(res["p_predict"])
+    if p_pred_samples:
+        res["p_pred_samples"] = np.zeros((K, cfg.kept, C))
+        o.p_pred_samples = _lib.dptr(res["p_pred_samples"])
+    if p_predict_sum:
+        res["p_predict_sum"] = np.zeros((C, N_LEVELS))
+        o.p_predict_sum = _lib.dptr(res["p_predict_sum"])
     cb = Combined()
     result = np.zeros((P, N_LEVELS))
     cb.result = _lib.dptr(result)
     result2 = np.zeros((C, N_LEVELS)) if n_test else None
     cb.result2 = _lib.dptr(result2) if n_test else None
+    result3 = np.zeros((C, N_LEVELS)) if have_x else None
+    cb.result3 = _lib.dptr(result3)
     cb.method = _lib.MK_COMBINE_MEDIAN if method == "median" else _lib.MK_COMBINE_MEAN
     cb.max_iter, cb.tol = int(max_iter), float(tol)
 
@@ -80,6 +98,13 @@ def meta_fit_node(subsets, cfg, coords_test=None, devices=(0,), subset_base=0, m
     del keep
     out = {"result": result.T.copy(), "result2": None if result2 is None else result2.T.copy(),
            "exchange": "rccl" if cb.exchange else "copy", "comm_ranks": int(cb.comm_ranks)}
+    if result3 is not None:
+        out["result3"] = result3.T.copy()
+    for k in ("p_predict", "p_pred_samples"):
+        if k in res:
+            out[k] = [res[k][i].T.copy() for i in range(K)]
+    if "p_predict_sum" in res:
+        out["p_predict_sum"] = res["p_predict_sum"].T.copy()
     if "parameters" in res:
         out["parameters"] = [res["parameters"][i].T.copy() for i in range(K)]
     if "w_predict" in res:

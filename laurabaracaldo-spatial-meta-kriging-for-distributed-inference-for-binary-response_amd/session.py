@@ -122,11 +122,20 @@ class SamplerConfig:
         return c, keep
 
 
+def _x_test(x_test, q, n_test, p):
+    """x.test as libmk reads it ((q n_test) x p column-major, flat), or ValueError on another shape."""
+    xt = np.asarray(x_test, dtype=np.float64)
+    if xt.ndim != 2 or xt.shape != (q * n_test, p):
+        raise ValueError(f"error: x_test must be (q*n_test) x p = {q * n_test} x {p}, not {xt.shape}")
+    return _f64(xt.ravel(order="F"))
+
+
 class PackedProblem:
     """mk_problem of a list of subsets (the R layout libmk reads: per subset column-major coords,
-    location-major y / weights, (n_s q) x p design), with the arrays it points into kept alive."""
+    location-major y / weights, (n_s q) x p design), with the arrays it points into kept alive.
+    x_test: the test sites' covariates ((q n_test) x p, location-major rows), or None."""
 
-    def __init__(self, subsets, cfg, coords_test=None, subset_base=0):
+    def __init__(self, subsets, cfg, coords_test=None, subset_base=0, x_test=None):
         self.n_part = np.ascontiguousarray([s["coords"].shape[0] for s in subsets], dtype=np.int32)
         self.S = len(subsets)
         self.coords = _f64(np.concatenate([np.asarray(s["coords"], float).ravel(order="F") for s in subsets]))
@@ -144,6 +153,8 @@ class PackedProblem:
         pr.coords, pr.y, pr.weights, pr.x = dptr(self.coords), dptr(self.y), dptr(self.weights), dptr(self.x)
         pr.n_test = self.n_test
         pr.coords_test = dptr(self.coords_test) if self.coords_test is not None else None
+        self.x_test = None if x_test is None else _x_test(x_test, cfg.q, self.n_test, cfg.p)
+        pr.x_test = dptr(self.x_test)
         self.c = pr
 
 
@@ -153,13 +164,15 @@ class Session:
     subsets: list of dicts with 'coords' (n_s,2), 'y' (n_s*q,), 'weights' (n_s*q,), 'x' (n_s*q, p).
     """
 
-    def __init__(self, subsets, cfg, coords_test=None, subset_base=0, device=0, record_w=False, lookahead=None):
-        lib = _lib.load()
+    def __init__(self, subsets, cfg, coords_test=None, subset_base=0, device=0, record_w=False, lookahead=None,
+                 x_test=None):
         self.cfg = cfg
         self.q, self.p = cfg.q, cfg.p
-        self._prob = PackedProblem(subsets, cfg, coords_test, subset_base)
+        self._prob = PackedProblem(subsets, cfg, coords_test, subset_base, x_test=x_test)
+        lib = _lib.load()
         self.n_part, self.S = self._prob.n_part, self._prob.S
         self.n_test, self.coords_test = self._prob.n_test, self._prob.coords_test
+        self.x_test = self._prob.x_test          # the test sites' covariates (flat, column-major) or None
         pr = self._prob.c
         c, self._keep = cfg.to_c(device=device, record_w=record_w)
         self.record_w = record_w
@@ -187,28 +200,46 @@ class Session:
         st["iteration"] = self.iteration
         return st
 
-    def set_test_sites(self, coords_test):
+    def set_test_sites(self, coords_test, x_test=None):
         """Kriging sites for the next outputs() of a session created with predict_tile > 0
-        (its kept chain states were recorded during the run): spPredict without refitting."""
+        (its kept chain states were recorded during the run): spPredict without refitting.
+        x_test ((q n_test) x p): their covariates, for the predictive probabilities; the covariates
+        of the earlier sites are dropped either way."""
         ct = np.asarray(coords_test, float).reshape(-1, 2)
+        xt = None if x_test is None else _x_test(x_test, self.q, int(ct.shape[0]), self.p)
         self.n_test = int(ct.shape[0])
         self.coords_test = _f64(ct.ravel(order="F"))
+        self.x_test = None
         check(self._lib.mk_session_set_test_sites(self._h, self.n_test, dptr(self.coords_test)))
+        if xt is not None:
+            self.set_test_covars(xt, _flat=True)
+
+    def set_test_covars(self, x_test, _flat=False):
+        """Covariates ((q n_test) x p) of the current test sites (mk_session_set_test_covars)."""
+        xt = x_test if _flat else _x_test(x_test, self.q, self.n_test, self.p)
+        check(self._lib.mk_session_set_test_covars(self._h, dptr(xt)))
+        self.x_test = xt
 
     def grids_device(self, which, out_ptr):
-        """Write the shard's (S, C, 200) grids -- which 0 parameters, 1 w.predict -- into device memory
+        """Write the shard's (S, C, 200) grids -- which 0 parameters, 1 w.predict, 2 p.predict -- into device memory
         at out_ptr (HBM of the session's device, e.g. a torch CUDA tensor's data_ptr()): the
         device-resident combine's input, no host round trip."""
         check(self._lib.mk_session_grids(self._h, int(which), ctypes.c_void_p(int(out_ptr)), 1))
 
-    def tile_grids(self, t0):
+    def tile_grids(self, t0, prob=False):
         """Tiled session (predict_tile > 0), after the run: (S, 200, q*Tc) w.predict grids of test
-        sites [t0, t0 + Tc) -- one tile's kriging replay only (configs[4]'s per-tile combine)."""
+        sites [t0, t0 + Tc) -- one tile's kriging replay only (configs[4]'s per-tile combine).
+        prob=True: (w grids, p.predict grids) of the same replay (needs x_test)."""
         T = self.predict_tile
         Tc = min(T, self.n_test - int(t0))
         out = np.zeros((self.S, self.q * Tc, _lib.N_LEVELS))
-        check(self._lib.mk_session_tile_grids(self._h, int(t0), out.ctypes.data_as(ctypes.c_void_p), 0))
-        return np.ascontiguousarray(np.transpose(out, (0, 2, 1)))
+        if not prob:
+            check(self._lib.mk_session_tile_grids(self._h, int(t0), out.ctypes.data_as(ctypes.c_void_p), 0))
+            return np.ascontiguousarray(np.transpose(out, (0, 2, 1)))
+        outp = np.zeros_like(out)
+        check(self._lib.mk_session_tile_grids_wp(self._h, int(t0), out.ctypes.data_as(ctypes.c_void_p),
+                                                 outp.ctypes.data_as(ctypes.c_void_p), 0))
+        return (np.ascontiguousarray(np.transpose(out, (0, 2, 1))), np.ascontiguousarray(np.transpose(outp, (0, 2, 1))))
 
     def set_kept_window(self, first, last):
         """Replay only iterations first..last (1-based; spPredict's start / end) in the next outputs()."""
@@ -258,13 +289,29 @@ class Session:
         return dict(launches=n.value, ms=ms.value, flops=fl.value)
 
     def outputs(self, quantiles=True, samples=False, w_samples=False, w_pred_samples=False, acceptance=False,
-                w_predict_sum=False, w_predict=True):
+                w_predict_sum=False, w_predict=True, p_predict=None, p_pred_samples=False, p_predict_sum=False):
         """quantiles: obj[[i]]$parameters (and $w.predict unless w_predict=False -- at 1M test sites the
-        per-subset grids are 1.6 GB each; w_predict_sum gives this shard's term of the combine)."""
+        per-subset grids are 1.6 GB each; w_predict_sum gives this shard's term of the combine).
+        p_predict / p_pred_samples / p_predict_sum: the same three of p(y = 1) = linkinv(x.test beta + w)
+        per kept state (they need x_test); p_predict defaults to on when quantiles is and the session has
+        covariates."""
         cfg = self.cfg
         S, P, q = self.S, cfg.P, cfg.q
         o = Outputs()
         res = {}
+        if p_predict is None:
+            p_predict = bool(quantiles) and self.x_test is not None and bool(self.n_test)
+        kept = getattr(self, "_window", cfg.kept)
+        C = q * self.n_test
+        if p_predict:
+            res["p_predict"] = np.zeros((S, C, _lib.N_LEVELS))
+            o.p_predict = dptr(res["p_predict"])
+        if p_pred_samples:
+            res["p_pred_samples"] = np.zeros((S, kept, C))
+            o.p_pred_samples = dptr(res["p_pred_samples"])
+        if p_predict_sum:
+            res["p_predict_sum"] = np.zeros((C, _lib.N_LEVELS))
+            o.p_predict_sum = dptr(res["p_predict_sum"])
         if quantiles:
             res["parameters"] = np.zeros((S, P, _lib.N_LEVELS))
             o.parameters = dptr(res["parameters"])
@@ -308,6 +355,12 @@ class Session:
             out["w_pred_samples"] = [res["w_pred_samples"][i].T.copy() for i in range(S)]  # (q n_test) x kept
         if "w_predict_sum" in res:
             out["w_predict_sum"] = res["w_predict_sum"].T.copy()                               # 200 x q*n_test
+        if "p_predict" in res:
+            out["p_predict"] = [res["p_predict"][i].T.copy() for i in range(S)]            # 200 x q*n_test
+        if "p_pred_samples" in res:
+            out["p_pred_samples"] = [res["p_pred_samples"][i].T.copy() for i in range(S)]  # (q n_test) x kept
+        if "p_predict_sum" in res:
+            out["p_predict_sum"] = res["p_predict_sum"].T.copy()                               # 200 x q*n_test
         if "acceptance" in res:
             out["acceptance"] = [res["acceptance"][i].T.copy() for i in range(S)]          # n_batch x nrep
         return out

@@ -129,7 +129,9 @@ def spMvGLM(formula, coords, weights, starting, tuning, priors, amcmc, cov_model
 
 def spPredict(sp_obj, pred_coords, pred_covars=None, start=1, end=None, thin=1):
     """p.w.predictive.samples ((q n_test) x kept) for kept iterations start..end (1-based,
-    inclusive; every thin-th), kriged from the chain states spMvGLM recorded (no refit)."""
+    inclusive; every thin-th), kriged from the chain states spMvGLM recorded (no refit).
+    With pred_covars ((q n_test) x p, location-major rows) also p.y.predictive.samples: spBayes's
+    binomial prediction linkinv(x(s)' beta + w(s)), beta and w(s) of the same iteration."""
     ses = sp_obj.get("_session")
     if ses is None:
         raise ValueError("error: the spMvGLM fit was closed; spPredict needs its recorded chain states")
@@ -138,8 +140,16 @@ def spPredict(sp_obj, pred_coords, pred_covars=None, start=1, end=None, thin=1):
     start = int(start)
     if not (1 <= start <= end <= n_samples):
         raise ValueError("error: invalid start/end")
-    ses.set_test_sites(np.asarray(pred_coords, float).reshape(-1, 2))
+    ct = np.asarray(pred_coords, float).reshape(-1, 2)
+    if pred_covars is not None:
+        xt = np.asarray(pred_covars, float)
+        if xt.ndim != 2 or xt.shape[0] != ses.q * ct.shape[0]:
+            raise ValueError("error: pred.covars must have one row per prediction site and outcome (q * n rows)")
+    ses.set_test_sites(ct, x_test=pred_covars)
     ses.set_kept_window(start, end)
-    out = ses.outputs(quantiles=False, w_pred_samples=True)
+    out = ses.outputs(quantiles=False, w_pred_samples=True, p_pred_samples=pred_covars is not None)
     wp = out["w_pred_samples"][0]                  # (q n_test) x (end - start + 1)
-    return {"p.w.predictive.samples": wp[:, ::int(thin)]}
+    res = {"p.w.predictive.samples": wp[:, ::int(thin)]}
+    if pred_covars is not None:
+        res["p.y.predictive.samples"] = out["p_pred_samples"][0][:, ::int(thin)]
+    return res

@@ -9,7 +9,8 @@
 #   MK.R:100-114  cl <- makeCluster(n.core); obj <- foreach(i = 1:n.core, ...) %dopar%
 #                 partitioned_spMvGLM(i, ...)
 #                 -> obj <- mk_meta_fit(y, x, weight, q, n.part, index.part, coords, coords.test,
-#                                       devices = 0:7)    (every GPU of the node, one call)
+#                                       devices = 0:7, x.test = x.test)
+#                                                         (every GPU of the node, one call)
 #   MK.R:123-133  result / result2 as the mean of the subset grids -> mk_combine(obj)
 #   MK.R:136-165  resampling, p(y = 1) and quantiles              -> mk_posterior_summary(...)
 # The worker's statistics that R computes before spMvGLM stay in R (MK.R:53-64): glm start
@@ -69,17 +70,24 @@ mk_glm_start <- function(y, x, weight, link = c("logit", "probit"), device = NUL
 # device: RCCL over xGMI).  Returns a list of K list(parameters = 200 x P, w.predict =
 # 200 x q n_test, acceptance) -- the shape partitioned_spMvGLM returns (MK.R:89) -- with the
 # combined grids (MK.R:127, 133; combine = "median": the Weiszfeld extension) as attribute
-# "combined", which mk_combine(obj) returns without recomputing.
+# "combined", which mk_combine(obj) returns without recomputing.  With x.test ((q n_test) x p, the
+# covariates MK.R:87 hands spPredict) every obj[[k]] also holds p.predict (200 x q n_test: the
+# 200-level grid of p(y = 1) = linkinv(x.test beta + w) over the kept iterations) and "combined"
+# holds result3, their combination.
 mk_meta_fit <- function(y, x, weight, q, n.part, index.part, coords, coords.test,
                         n.batch = 100, batch.length = 50, accept.rate = 0.43,
                         cov.model = c("exponential", "matern"), link = c("logit", "probit"),
                         predict.tile = 0L, devices = 0L, glm.on.device = FALSE, n.report = 10,
-                        combine = c("mean", "median")) {
+                        combine = c("mean", "median"), x.test = NULL) {
   cov.model <- match.arg(cov.model)
   link <- match.arg(link)
   combine <- match.arg(combine)
   coords <- .mk_coords(coords, "coords")
   coords.test <- .mk_coords(coords.test, "coords.test")
+  if (!is.null(x.test)) {
+    x.test <- as.matrix(x.test) * 1.0
+    if (nrow(x.test) != q * nrow(coords.test) || ncol(x.test) != ncol(x)) stop("error: x.test must be (q * n.test) x p")
+  }
   st <- mk_glm_start(y, x, weight, link, if (glm.on.device) devices[1] else NULL)   # MK.R:53-55
   n.samples <- n.batch * batch.length
   cfg <- .mk_cfg(q, st$beta, st$tuning, n.batch, batch.length, accept.rate,
@@ -91,16 +99,20 @@ mk_meta_fit <- function(y, x, weight, q, n.part, index.part, coords, coords.test
                unlist(lapply(index.part, function(i) as.double(y[.mk_rows(i, q)]))),
                unlist(lapply(index.part, function(i) rep(as.double(weight), length(i) * q))),
                unlist(lapply(index.part, function(i) as.vector(x[.mk_rows(i, q), , drop = FALSE] * 1.0))),
-               coords.test, as.integer(q), ncol(x), cfg,
+               coords.test, x.test, as.integer(q), ncol(x), cfg,
                floor(runif(1) * 2^52),                                               # honours set.seed
                as.integer(devices), as.integer(n.report), as.integer(combine == "median"))
   P <- length(res[[1]]) / (S * 200)
   C <- length(res[[2]]) / (S * 200)
-  obj <- lapply(seq_len(S), function(k) list(
-    parameters = matrix(res[[1]][(k - 1) * 200 * P + 1:(200 * P)], 200, P),
-    w.predict = matrix(res[[2]][(k - 1) * 200 * C + seq_len(200 * C)], 200, C),
-    acceptance = matrix(res[[3]][(k - 1) * n.batch * (P + 1) + 1:(n.batch * (P + 1))], n.batch, P + 1)))
-  attr(obj, "combined") <- list(result = res[[4]], result2 = res[[5]], method = combine)
+  obj <- lapply(seq_len(S), function(k) {
+    o <- list(
+      parameters = matrix(res[[1]][(k - 1) * 200 * P + 1:(200 * P)], 200, P),
+      w.predict = matrix(res[[2]][(k - 1) * 200 * C + seq_len(200 * C)], 200, C),
+      acceptance = matrix(res[[3]][(k - 1) * n.batch * (P + 1) + 1:(n.batch * (P + 1))], n.batch, P + 1))
+    if (!is.null(res[[6]])) o$p.predict <- matrix(res[[6]][(k - 1) * 200 * C + seq_len(200 * C)], 200, C)
+    o
+  })
+  attr(obj, "combined") <- list(result = res[[4]], result2 = res[[5]], result3 = res[[7]], method = combine)
   obj
 }
 
@@ -176,16 +188,21 @@ mk_spMvGLM <- function(formula, coords, weights, starting, tuning, priors, amcmc
 
 # spPredict(sp.obj, pred.coords, pred.covars, start, end, thin) as MK.R:87 calls it:
 # p.w.predictive.samples ((q n_test) x kept, location-major rows) kriged from the recorded chain
-# states of iterations start..end (no refit).  pred.covars is accepted for the reference's
-# signature; the latent field's predictive draws (the only output MK.R:89 uses) do not need it.
+# states of iterations start..end (no refit).  With pred.covars ((q n_test) x p, location-major
+# rows) also spBayes's p.y.predictive.samples for the binomial family: linkinv(x(s)' beta + w(s)),
+# beta and w(s) of the same iteration.
 mk_spPredict <- function(sp.obj, pred.coords, pred.covars = NULL, start = 1, end = sp.obj$n.samples, thin = 1) {
   if (!inherits(sp.obj, "mk_spMvGLM")) stop("error: sp.obj must come from mk_spMvGLM")
   start <- as.integer(start)
   end <- as.integer(end)
   if (start < 1L || end < start || end > sp.obj$n.samples) stop("error: invalid start/end")
-  wp <- .Call("mk_r_sppredict", sp.obj$session, .mk_coords(pred.coords, "pred.coords"), start, end,
-              as.integer(sp.obj$q))
-  list(p.w.predictive.samples = wp[, seq(1, ncol(wp), by = thin), drop = FALSE])
+  if (!is.null(pred.covars)) pred.covars <- as.matrix(pred.covars) * 1.0
+  res <- .Call("mk_r_sppredict", sp.obj$session, .mk_coords(pred.coords, "pred.coords"), pred.covars, start, end,
+               as.integer(sp.obj$q))
+  keep <- seq(1, ncol(res[[1]]), by = thin)
+  out <- list(p.w.predictive.samples = res[[1]][, keep, drop = FALSE])
+  if (!is.null(res[[2]])) out$p.y.predictive.samples <- res[[2]][, keep, drop = FALSE]
+  out
 }
 
 # MK.R:136-165 on the combined grids.  The resample index is drawn here by R itself, exactly as

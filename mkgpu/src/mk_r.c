@@ -8,8 +8,9 @@
  *                      / _outputs                stays alive for spPredict, owned by an external
  *                                                pointer whose finalizer destroys it)
  *   mk_r_sppredict  -> mk_session_set_test_sites MK.R:87 (spPredict(m.1, coords.test, x.test,
- *                      / _set_kept_window        start, end): kriging replayed from the recorded
- *                      / _outputs                chain states, no refit)
+ *                      / _set_test_covars        start, end): kriging replayed from the recorded
+ *                      / _set_kept_window        chain states, no refit; with x.test also
+ *                      / _outputs                p.y.predictive.samples)
  *   mk_r_combine    -> mk_combine                MK.R:123-133 (quantile-average combine)
  *   mk_r_summary    -> mk_posterior_summary_ex   MK.R:136-165 (resample, p(y = 1), quantiles)
  *   mk_r_glm        -> mk_glm_binomial_link      MK.R:53-55   (glm start values, on the device)
@@ -95,8 +96,8 @@ static void read_config(SEXP cfg, SEXP seed, mk_config* c) {
 }
 
 /* subsets back to back: coords n_s x 2 column-major, y / weights location-major, x (n_s q) x p */
-static void read_problem(SEXP n_part, SEXP coords, SEXP y, SEXP weights, SEXP x, SEXP coords_test, SEXP q, SEXP p,
-                         mk_problem* pr) {
+static void read_problem(SEXP n_part, SEXP coords, SEXP y, SEXP weights, SEXP x, SEXP coords_test, SEXP x_test, SEXP q,
+                         SEXP p, mk_problem* pr) {
   memset(pr, 0, sizeof *pr);
   pr->n_subsets = LENGTH(n_part);
   pr->subset_base = 0;
@@ -109,6 +110,7 @@ static void read_problem(SEXP n_part, SEXP coords, SEXP y, SEXP weights, SEXP x,
   pr->x = REAL(x);
   pr->n_test = isNull(coords_test) ? 0 : nrows(coords_test);
   pr->coords_test = dp(coords_test);
+  pr->x_test = dp(x_test); /* (q n_test) x p, or NULL: no predictive probabilities */
 }
 
 static int n_params(const mk_config* c, int np, int q) {
@@ -117,13 +119,15 @@ static int n_params(const mk_config* c, int np, int q) {
 
 /* MK.R:100-133 over the GPUs in `devices`: every subset's grids plus the combined grids.
  * combine: 0 = the reference's mean (MK.R:123-133), 1 = Weiszfeld W2 median.
+ * x_test ((q n_test) x p, or NULL): MK.R:87's x.test; with it the grids of p(y = 1) too.
  * Returns list(parameters = S x 200 x P, w.predict = S x 200 x q n_test, acceptance,
- *              result = 200 x P, result2 = 200 x q n_test). */
-SEXP mk_r_fit(SEXP n_part, SEXP coords, SEXP y, SEXP weights, SEXP x, SEXP coords_test, SEXP q, SEXP p,
+ *              result = 200 x P, result2 = 200 x q n_test,
+ *              p.predict = S x 200 x q n_test, result3 = 200 x q n_test (both NULL without x_test)). */
+SEXP mk_r_fit(SEXP n_part, SEXP coords, SEXP y, SEXP weights, SEXP x, SEXP coords_test, SEXP x_test, SEXP q, SEXP p,
               SEXP cfg, SEXP seed, SEXP devices, SEXP report, SEXP combine) {
   mk_problem pr;
   mk_config c;
-  read_problem(n_part, coords, y, weights, x, coords_test, q, p, &pr);
+  read_problem(n_part, coords, y, weights, x, coords_test, x_test, q, p, &pr);
   read_config(cfg, seed, &c);
   const int S = pr.n_subsets, np = LENGTH(VECTOR_ELT(cfg, 5));
   const int P = n_params(&c, np, pr.q);
@@ -134,27 +138,34 @@ SEXP mk_r_fit(SEXP n_part, SEXP coords, SEXP y, SEXP weights, SEXP x, SEXP coord
   SEXP acc = PROTECT(allocVector(REALSXP, (R_xlen_t)S * c.n_batch * n_acc));
   SEXP r1 = PROTECT(allocMatrix(REALSXP, MK_N_LEVELS, P));
   SEXP r2 = PROTECT(allocMatrix(REALSXP, MK_N_LEVELS, (int)C));
+  const int prob = pr.x_test != NULL && pr.n_test > 0;
+  SEXP ppr = PROTECT(prob ? allocVector(REALSXP, (R_xlen_t)S * MK_N_LEVELS * C) : R_NilValue);
+  SEXP r3 = PROTECT(prob ? allocMatrix(REALSXP, MK_N_LEVELS, (int)C) : R_NilValue);
   mk_outputs o;
   memset(&o, 0, sizeof o);
   o.parameters = REAL(par);
   o.w_predict = pr.n_test ? REAL(wpr) : NULL;
   o.acceptance = REAL(acc);
+  o.p_predict = dp(ppr);
   mk_combined cb;
   memset(&cb, 0, sizeof cb);
   cb.result = REAL(r1);
   cb.result2 = pr.n_test ? REAL(r2) : NULL;
+  cb.result3 = dp(r3);
   cb.method = asInteger(combine);
   cb.max_iter = 100;
   cb.tol = 1e-12;
   progress_t pg = {asInteger(report), c.n_batch, c.batch_length, 0};
-  if (mk_meta_fit(&pr, &c, INTEGER(devices), LENGTH(devices), r_progress, &pg, &o, &cb) != MK_OK) fail(5);
-  SEXP res = PROTECT(allocVector(VECSXP, 5));
+  if (mk_meta_fit(&pr, &c, INTEGER(devices), LENGTH(devices), r_progress, &pg, &o, &cb) != MK_OK) fail(7);
+  SEXP res = PROTECT(allocVector(VECSXP, 7));
   SET_VECTOR_ELT(res, 0, par);
   SET_VECTOR_ELT(res, 1, wpr);
   SET_VECTOR_ELT(res, 2, acc);
   SET_VECTOR_ELT(res, 3, r1);
   SET_VECTOR_ELT(res, 4, r2);
-  UNPROTECT(6);
+  SET_VECTOR_ELT(res, 5, ppr);
+  SET_VECTOR_ELT(res, 6, r3);
+  UNPROTECT(8);
   return res;
 }
 
@@ -172,7 +183,7 @@ SEXP mk_r_spmvglm(SEXP coords, SEXP y, SEXP weights, SEXP x, SEXP q, SEXP cfg, S
   mk_problem pr;
   mk_config c;
   SEXP n_part = PROTECT(ScalarInteger(nrows(coords)));
-  read_problem(n_part, coords, y, weights, x, R_NilValue, q, ScalarInteger(ncols(x)), &pr);
+  read_problem(n_part, coords, y, weights, x, R_NilValue, R_NilValue, q, ScalarInteger(ncols(x)), &pr);
   read_config(cfg, seed, &c);
   c.burn_in = 1;                         /* record every iteration's state: spPredict picks start..end */
   if (c.predict_tile <= 0) c.predict_tile = 65536;
@@ -211,22 +222,32 @@ SEXP mk_r_spmvglm(SEXP coords, SEXP y, SEXP weights, SEXP x, SEXP q, SEXP cfg, S
   return res;
 }
 
-/* spPredict(sp.obj, pred.coords, start, end): p.w.predictive.samples ((q n_test) x (end - start + 1)),
- * kriged from the recorded states of iterations start..end (1-based) of the spMvGLM session. */
-SEXP mk_r_sppredict(SEXP session, SEXP coords_test, SEXP start, SEXP end, SEXP q) {
+/* spPredict(sp.obj, pred.coords, pred.covars, start, end): list(p.w.predictive.samples,
+ * p.y.predictive.samples), both (q n_test) x (end - start + 1), kriged from the recorded states of
+ * iterations start..end (1-based) of the spMvGLM session; x_test ((q n_test) x p) is pred.covars, and
+ * without it (NULL) the second entry is NULL. */
+SEXP mk_r_sppredict(SEXP session, SEXP coords_test, SEXP x_test, SEXP start, SEXP end, SEXP q) {
   mk_session* s = (mk_session*)R_ExternalPtrAddr(session);
   if (!s) Rf_error("libmk: the spMvGLM session was freed");
   const int n_test = nrows(coords_test), first = asInteger(start), last = asInteger(end);
+  const int prob = !isNull(x_test);
+  if (prob && nrows(x_test) != asInteger(q) * n_test) Rf_error("libmk: pred.covars must have q * nrow(pred.coords) rows");
   if (mk_session_set_test_sites(s, n_test, REAL(coords_test)) != MK_OK ||
+      (prob && mk_session_set_test_covars(s, REAL(x_test)) != MK_OK) ||
       mk_session_set_kept_window(s, first, last) != MK_OK)
     fail(0);
   SEXP wp = PROTECT(allocMatrix(REALSXP, asInteger(q) * n_test, last - first + 1));
+  SEXP pp = PROTECT(prob ? allocMatrix(REALSXP, asInteger(q) * n_test, last - first + 1) : R_NilValue);
   mk_outputs o;
   memset(&o, 0, sizeof o);
   o.w_pred_samples = REAL(wp);
-  if (mk_session_outputs(s, &o) != MK_OK) fail(1);
-  UNPROTECT(1);
-  return wp;
+  o.p_pred_samples = dp(pp);
+  if (mk_session_outputs(s, &o) != MK_OK) fail(2);
+  SEXP res = PROTECT(allocVector(VECSXP, 2));
+  SET_VECTOR_ELT(res, 0, wp);
+  SET_VECTOR_ELT(res, 1, pp);
+  UNPROTECT(3);
+  return res;
 }
 
 /* grids: K x len doubles (the K subset grids back to back, each column-major as R holds it).
@@ -305,9 +326,9 @@ SEXP mk_r_shutdown(void) {
 }
 
 static const R_CallMethodDef call_methods[] = {
-    {"mk_r_fit", (DL_FUNC)&mk_r_fit, 13},
+    {"mk_r_fit", (DL_FUNC)&mk_r_fit, 14},
     {"mk_r_spmvglm", (DL_FUNC)&mk_r_spmvglm, 8},
-    {"mk_r_sppredict", (DL_FUNC)&mk_r_sppredict, 5},
+    {"mk_r_sppredict", (DL_FUNC)&mk_r_sppredict, 6},
     {"mk_r_combine", (DL_FUNC)&mk_r_combine, 4},
     {"mk_r_summary", (DL_FUNC)&mk_r_summary, 6},
     {"mk_r_glm", (DL_FUNC)&mk_r_glm, 5},

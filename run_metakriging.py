@@ -102,7 +102,9 @@ def main():
     P = cfg.P
     ses = None
     if subs:
-        ses = mk.Session(subs, cfg, coords_test=d["coords_test"], subset_base=lo, device=local)   # MK.R:108
+        # one process, fused kriging: x.test goes in as MK.R:87 passes it, p.predict comes out
+        ses = mk.Session(subs, cfg, coords_test=d["coords_test"], subset_base=lo, device=local,
+                         x_test=d["x_test"] if (world == 1 and not big) else None)            # MK.R:108
         for b in range(cfg.n_batch):          # progress every n.report = 10 batches (MK.R:84)
             ses.run(cfg.batch_length)
             if rank == 0 and (b + 1) % 10 == 0:
@@ -118,6 +120,7 @@ def main():
     t["predict_quantiles_s"] = time.perf_counter() - t3
 
     t4 = time.perf_counter()
+    result3 = None
     par = np.stack(out["parameters"]) if out["parameters"] else np.zeros((0, 200, P))
     tile = ses.predict_tile if ses is not None else cfg.predict_tile   # the tile in use (HBM may shrink it)
 
@@ -152,6 +155,9 @@ def main():
     elif not big:
         obj = [{"parameters": out["parameters"][i], "w.predict": out["w_predict"][i]} for i in range(len(subs))]
         result, result2 = mk.combine_results(obj, device=local, method=a.combine)             # MK.R:123-133
+        if "p_predict" in out:
+            result3 = mk.metakriging.combine_predictive([{"p.predict": g} for g in out["p_predict"]], device=local,
+                                                        method=a.combine)
     else:   # tiled kriging (cfg5), one process: every tile's K grids combined as they are replayed
         result = mk.combine_results([{"parameters": g} for g in out["parameters"]], device=local,
                                     method=a.combine)[0]
@@ -183,9 +189,22 @@ def main():
             wq = summ["w_quant"]
             rec["w_test_coverage_95"] = float(np.mean((d["w_test_true"] >= wq[1]) & (d["w_test_true"] <= wq[2])))
             rec["truth_beta_phi"] = truth.tolist()
+            rec.update(predictive_scores(result3, d))
         print(json.dumps(rec), flush=True)
     if dist is not None:
         dist.destroy_process_group()
+
+
+def predictive_scores(result3, d):
+    """Held-out scores of the combined grid of p(y = 1) (result3, 200 x q n_test; levels 0.005 .. 1):
+    the Brier score of its median against y.test, and how often the generating probability
+    logistic(x.test beta + w) lies in its 2.5 % .. 97.5 % band."""
+    if result3 is None:
+        return {}
+    med, lo, hi = result3[99], result3[4], result3[194]
+    p_true = 1.0 / (1.0 + np.exp(-(d["x_test"] @ d["beta_true"] + d["w_test_true"])))
+    return {"p_test_brier": float(np.mean((med - d["y_test"]) ** 2)),
+            "p_test_coverage_95": float(np.mean((p_true >= lo) & (p_true <= hi)))}
 
 
 def node_main(a, c):
@@ -206,7 +225,7 @@ def node_main(a, c):
     ph, result, result2, summ, cfg = mk.metakriging.reference_flow(
         d, K, q, cov_model=c["cov"], n_batch=c["n_batch"], batch_length=c["batch_length"], seed=a.seed,
         devices=devices, method=a.combine, predict_tile=c.get("predict_tile", 0), partition_method=a.partition,
-        progress=progress)
+        progress=progress, predictive=True)     # MK.R:87's x.test: the grids of p(y = 1) and result3
     ph["data_s"] = data_s
     rec = dict(config=a.config, workload=c, devices=devices, combine=a.combine, phases=ph,
                subset_iters_per_s=K * cfg.n_samples / ph["chains_s"])
@@ -216,6 +235,7 @@ def node_main(a, c):
     wq = summ["w_quant"]
     rec["w_test_coverage_95"] = float(np.mean((d["w_test_true"] >= wq[1]) & (d["w_test_true"] <= wq[2])))
     rec["truth_beta_phi"] = truth.tolist()
+    rec.update(predictive_scores(summ.get("result3"), d))
     print(json.dumps(rec), flush=True)
 
 
