@@ -852,43 +852,46 @@ int session_info(const mk_session* s, ShardInfo* in) {
   in->stream = s->stream;
   return 0;
 }
-// [S][P][200] parameter grids (obj[[i]]$parameters, MK.R:89) into d_out (HBM), on the session stream.
-int session_param_grids(mk_session* s, double* d_out) {
+// The 200-level grids of one kind from the recorded draws into d_out (HBM), on the session stream,
+// not waited for: [S][P][200] of the parameters (obj[[i]]$parameters, MK.R:89), or of a fused
+// session's kriging draws [S][q n_test][200] -- w.predict, or p = pred_prob(draw), transformed as the
+// sort's LDS is filled (no buffer of p draws).
+static int launch_grids(mk_session* s, GridKind kind, double* d_out) {
+  const Model& md = s->md;
+  if (kind == GRID_PARAMETERS)
+    return launch_quantiles(s->S * s->P, s->stream, md.samples + (long)md.kept0 * s->P, (long)md.n_samples * s->P,
+                            (long)s->P, md.n_kept, s->P, s->d_probs, MK_N_LEVELS, d_out);
+  const int C = s->q * md.n_test;
+  if (kind == GRID_P)
+    return launch_quantiles_prob(s->S * C, s->stream, md.w_pred, (long)md.n_kept * C, (long)C, md.n_kept, C, s->d_probs,
+                                 MK_N_LEVELS, d_out, prob_src(s, 0));
+  return launch_quantiles(s->S * C, s->stream, md.w_pred, (long)md.n_kept * C, (long)C, md.n_kept, C, s->d_probs,
+                          MK_N_LEVELS, d_out);
+}
+int session_grids(mk_session* s, GridKind kind, double* d_out) {
   MK_ENTRY_DEVICE(s->device);
-  Model& md = s->md;
-  if (s->iter < md.n_samples) return set_err(MK_E_ARG, "quantile outputs need all n.samples iterations");
-  const int rq = launch_quantiles(s->S * s->P, s->stream, md.samples + (long)md.kept0 * s->P, (long)md.n_samples * s->P,
-                                  (long)s->P, md.n_kept, s->P, s->d_probs, MK_N_LEVELS, d_out);
+  if (kind != GRID_PARAMETERS && s->tiled) return set_err(MK_E_ARG, "tiled sessions produce their grids per tile");
+  if (kind == GRID_P && !s->d_xt) return set_err(MK_E_ARG, "predictive probabilities need x_test");
+  if (s->iter < s->md.n_samples) return set_err(MK_E_ARG, "quantile outputs need all n.samples iterations");
+  const int rq = launch_grids(s, kind, d_out);
   if (rq) return rq;
   HIPCHK(hipStreamSynchronize(s->stream));
   return 0;
 }
-// [S][q n_test][200] w.predict grids of a fused session into d_out.
-int session_wpred_grids(mk_session* s, double* d_out) {
-  MK_ENTRY_DEVICE(s->device);
-  Model& md = s->md;
-  if (s->tiled) return set_err(MK_E_ARG, "tiled sessions produce their grids per tile");
-  if (s->iter < md.n_samples) return set_err(MK_E_ARG, "quantile outputs need all n.samples iterations");
-  const int C = s->q * md.n_test;
-  const int rq = launch_quantiles(s->S * C, s->stream, md.w_pred, (long)md.n_kept * C, (long)C, md.n_kept, C, s->d_probs,
-                                  MK_N_LEVELS, d_out);
-  if (rq) return rq;
-  HIPCHK(hipStreamSynchronize(s->stream));
-  return 0;
-}
-// [S][q n_test][200] p.predict grids of a fused session into d_out: the quantiles of
-// p = pred_prob(draw), transformed as the sort's LDS is filled (no buffer of p draws).
-int session_ppred_grids(mk_session* s, double* d_out) {
-  MK_ENTRY_DEVICE(s->device);
-  Model& md = s->md;
-  if (s->tiled) return set_err(MK_E_ARG, "tiled sessions produce their grids per tile");
-  if (!s->d_xt) return set_err(MK_E_ARG, "predictive probabilities need x_test");
-  if (s->iter < md.n_samples) return set_err(MK_E_ARG, "quantile outputs need all n.samples iterations");
-  const int C = s->q * md.n_test;
-  const int rq = launch_quantiles_prob(s->S * C, s->stream, md.w_pred, (long)md.n_kept * C, (long)C, md.n_kept, C,
-                                       s->d_probs, MK_N_LEVELS, d_out, prob_src(s, 0));
-  if (rq) return rq;
-  HIPCHK(hipStreamSynchronize(s->stream));
+int grids_to_host(mk_session* s, const double* d_grids, long Ct, long col0, long C, double* h_each, double* h_sum,
+                  double* dsum) {
+  const size_t row = (size_t)Ct * MK_N_LEVELS * 8;   // one subset's block
+  hipStream_t st = s->stream;
+  if (h_each && Ct == C)   // whole arrays: one flat copy
+    HIPCHK(hipMemcpyAsync(h_each, d_grids, (size_t)s->S * row, hipMemcpyDeviceToHost, st));
+  else if (h_each)
+    HIPCHK(hipMemcpy2DAsync(h_each + (size_t)col0 * MK_N_LEVELS, (size_t)C * MK_N_LEVELS * 8, d_grids, row, row, s->S,
+                            hipMemcpyDeviceToHost, st));
+  if (h_sum) {   // this shard's term of the combine: sequential sum over its subsets
+    MK_LAUNCH(k_combine, dim3((unsigned)((Ct * MK_N_LEVELS + 255) / 256)), dim3(256), 0, st, d_grids, s->S,
+              Ct * MK_N_LEVELS, dsum, 0);
+    HIPCHK(hipMemcpyAsync(h_sum + (size_t)col0 * MK_N_LEVELS, dsum, row, hipMemcpyDeviceToHost, st));
+  }
   return 0;
 }
 // Tiled session: the grids [S][q Tc][200] of test-site tile [t0, t0 + Tc) into d_out, those of the
@@ -915,7 +918,7 @@ extern "C" int mk_session_grids(mk_session* s, int32_t which, double* out, int32
   DevBufs scratch;
   double* d = out;
   if (!device_out && !(d = scratch.get<double>((size_t)s->S * C * MK_N_LEVELS))) return set_err(MK_E_NOMEM, "grid scratch");
-  const int rc = which == 0 ? session_param_grids(s, d) : which == 1 ? session_wpred_grids(s, d) : session_ppred_grids(s, d);
+  const int rc = session_grids(s, (GridKind)which, d);
   if (rc) return rc;
   if (!device_out) HIPCHK(hipMemcpy(out, d, (size_t)s->S * C * MK_N_LEVELS * 8, hipMemcpyDeviceToHost));
   return 0;
@@ -947,6 +950,14 @@ extern "C" int mk_session_tile_grids(mk_session* s, int32_t t0, double* out, int
   return mk_session_tile_grids_wp(s, t0, out, nullptr, device_out);
 }
 
+// A downloaded device array, row-major [rows][ld], into the caller's layout: element (r, c), c < cols,
+// goes to dst[r * dr + c * dc], and rows >= valid are written as zero (iterations not run yet).  A
+// column-major rows x cols destination is dr = 1, dc = rows.
+static void host_layout(double* dst, size_t dr, size_t dc, const double* src, int rows, int cols, size_t ld, int valid) {
+  for (int r = 0; r < rows; ++r)
+    for (int c = 0; c < cols; ++c) dst[r * dr + c * dc] = r < valid ? src[r * ld + c] : 0.0;
+}
+
 extern "C" int mk_session_outputs(mk_session* s, mk_outputs* o) {
   if (!s || !o) return set_err(MK_E_ARG, "null session/outputs");
   if (s->poisoned) return set_err(MK_E_HIP, std::string("session unusable after an earlier failure: ") + s->poisoned);
@@ -962,32 +973,21 @@ extern "C" int mk_session_outputs(mk_session* s, mk_outputs* o) {
     return set_err(MK_E_ARG, "p_predict / p_pred_samples / p_predict_sum need x_test (mk_problem.x_test or "
                              "mk_session_set_test_covars)");
   DevBufs scratch;
-  if (o->parameters) {
-    double* dq = scratch.get<double>((size_t)S * P * MK_N_LEVELS);
-    if (!dq) return set_err(MK_E_NOMEM, "quantile scratch");
-    int rq = launch_quantiles(S * P, s->stream, md.samples + (long)md.kept0 * P, (long)md.n_samples * P, (long)P,
-                              md.n_kept, P, s->d_probs, MK_N_LEVELS, dq);
-    if (rq) return rq;
-    // device layout [S][P][200] == R's 200 x P column-major per subset
-    HIPCHK(hipMemcpyAsync(o->parameters, dq, (size_t)S * P * MK_N_LEVELS * 8, hipMemcpyDeviceToHost, s->stream));
-  }
-  if (!s->tiled && (o->p_predict || o->p_predict_sum)) {   // fused: the same draws, transformed on load
-    const int C = q * n_test;
+  // One kind's grids (parameters, or a fused session's w / p) through scratch of their own to the
+  // host; the device layout [S][C][200] == R's 200 x C column-major per subset.
+  auto grids = [&](GridKind kind, double* h_each, double* h_sum) -> int {
+    const long C = kind == GRID_PARAMETERS ? P : (long)q * n_test;
     double* dq = scratch.get<double>((size_t)S * C * MK_N_LEVELS);
     if (!dq) return set_err(MK_E_NOMEM, "quantile scratch");
-    int rq = launch_quantiles_prob(S * C, s->stream, md.w_pred, (long)md.n_kept * C, (long)C, md.n_kept, C, s->d_probs,
-                                   MK_N_LEVELS, dq, prob_src(s, 0));
-    if (rq) return rq;
-    if (o->p_predict)
-      HIPCHK(hipMemcpyAsync(o->p_predict, dq, (size_t)S * C * MK_N_LEVELS * 8, hipMemcpyDeviceToHost, s->stream));
-    if (o->p_predict_sum) {
-      double* dsum = scratch.get<double>((size_t)C * MK_N_LEVELS);
-      if (!dsum) return set_err(MK_E_NOMEM, "combine scratch");
-      MK_LAUNCH(k_combine, dim3((unsigned)(((long)C * MK_N_LEVELS + 255) / 256)), dim3(256), 0, s->stream, dq,
-                         S, (long)C * MK_N_LEVELS, dsum, 0);
-      HIPCHK(hipMemcpyAsync(o->p_predict_sum, dsum, (size_t)C * MK_N_LEVELS * 8, hipMemcpyDeviceToHost, s->stream));
-    }
-  }
+    double* dsum = h_sum ? scratch.get<double>((size_t)C * MK_N_LEVELS) : nullptr;
+    if (h_sum && !dsum) return set_err(MK_E_NOMEM, "combine scratch");
+    const int rq = launch_grids(s, kind, dq);
+    return rq ? rq : grids_to_host(s, dq, C, 0, C, h_each, h_sum, dsum);
+  };
+  int rg;
+  if (o->parameters && (rg = grids(GRID_PARAMETERS, o->parameters, nullptr))) return rg;
+  // fused: p before w (the same draws, transformed on load)
+  if (!s->tiled && (o->p_predict || o->p_predict_sum) && (rg = grids(GRID_P, o->p_predict, o->p_predict_sum))) return rg;
   if (!s->tiled && o->p_pred_samples) {   // per subset C x kept column-major == the device's [kept][C]
     const int C = q * n_test;
     double* dp = scratch.get<double>((size_t)md.n_kept * C);
@@ -1003,66 +1003,36 @@ extern "C" int mk_session_outputs(mk_session* s, mk_outputs* o) {
     if (rc) return rc;
     if (s->prof.on) drain_timers(s);
   } else if ((o->w_predict || o->w_predict_sum) && n_test > 0) {
-    const int C = q * n_test;
-    double* dq = scratch.get<double>((size_t)S * C * MK_N_LEVELS);
-    if (!dq) return set_err(MK_E_NOMEM, "quantile scratch");
-    int rq = launch_quantiles(S * C, s->stream, md.w_pred, (long)md.n_kept * C, (long)C, md.n_kept, C, s->d_probs,
-                              MK_N_LEVELS, dq);
-    if (rq) return rq;
-    if (o->w_predict)
-      HIPCHK(hipMemcpyAsync(o->w_predict, dq, (size_t)S * C * MK_N_LEVELS * 8, hipMemcpyDeviceToHost, s->stream));
-    if (o->w_predict_sum) {   // this shard's term of the combine: sequential sum over its subsets
-      double* dsum = scratch.get<double>((size_t)C * MK_N_LEVELS);
-      if (!dsum) return set_err(MK_E_NOMEM, "combine scratch");
-      MK_LAUNCH(k_combine, dim3((unsigned)(((long)C * MK_N_LEVELS + 255) / 256)), dim3(256), 0, s->stream, dq,
-                         S, (long)C * MK_N_LEVELS, dsum, 0);
-      HIPCHK(hipMemcpyAsync(o->w_predict_sum, dsum, (size_t)C * MK_N_LEVELS * 8, hipMemcpyDeviceToHost, s->stream));
-    }
+    if ((rg = grids(GRID_W, o->w_predict, o->w_predict_sum))) return rg;
   }
   HIPCHK(hipStreamSynchronize(s->stream));
-  const int it = s->iter;
-  if (o->samples) {
-    std::vector<double> h((size_t)S * md.n_samples * P);
+  const int it = s->iter, n = md.n_samples;
+  std::vector<double> h;
+  if (o->samples) {   // [S][iter][P] -> per subset n_samples x P column-major
+    h.resize((size_t)S * n * P);
     HIPCHK(hipMemcpy(h.data(), md.samples, h.size() * 8, hipMemcpyDeviceToHost));
-    // [S][iter][P] -> per subset n_samples x P column-major (rows beyond `it` are zero)
-    for (int i = 0; i < S; ++i)
-      for (int r = 0; r < md.n_samples; ++r)
-        for (int cc = 0; cc < P; ++cc)
-          o->samples[(size_t)i * md.n_samples * P + r + (size_t)cc * md.n_samples] =
-              (r < it) ? h[((size_t)i * md.n_samples + r) * P + cc] : 0.0;
+    for (size_t i = 0; i < (size_t)S; ++i) host_layout(o->samples + i * n * P, 1, n, h.data() + i * n * P, n, P, P, it);
   }
-  if (o->w_samples) {
+  if (o->w_samples) {   // [S][iter][Np] -> per subset N x n_samples column-major: a state's N valid entries are a column
     if (!md.w_samples) return set_err(MK_E_ARG, "w samples were not recorded (record_w = 0)");
-    std::vector<double> h((size_t)S * md.n_samples * md.Np);
+    h.resize((size_t)S * n * md.Np);
     HIPCHK(hipMemcpy(h.data(), md.w_samples, h.size() * 8, hipMemcpyDeviceToHost));
     size_t off = 0;
     for (int i = 0; i < S; ++i) {
       const int N = s->n_part[i] * q;
-      for (int r = 0; r < md.n_samples; ++r)
-        for (int k = 0; k < N; ++k)
-          o->w_samples[off + k + (size_t)r * N] = (r < it) ? h[((size_t)i * md.n_samples + r) * md.Np + k] : 0.0;
-      off += (size_t)N * md.n_samples;
+      host_layout(o->w_samples + off, N, 1, h.data() + (size_t)i * n * md.Np, n, N, md.Np, it);
+      off += (size_t)N * n;
     }
   }
-  if (o->w_pred_samples && n_test > 0 && !s->tiled) {
-    const int C = q * n_test;
-    std::vector<double> h((size_t)S * md.n_kept * C);
-    HIPCHK(hipMemcpy(h.data(), md.w_pred, h.size() * 8, hipMemcpyDeviceToHost));
-    // [S][kept][C] -> per subset C x kept column-major (p.w.predictive.samples)
-    for (int i = 0; i < S; ++i)
-      for (int k = 0; k < md.n_kept; ++k)
-        for (int cc = 0; cc < C; ++cc)
-          o->w_pred_samples[(size_t)i * md.n_kept * C + cc + (size_t)k * C] = h[((size_t)i * md.n_kept + k) * C + cc];
-  }
-  if (o->acceptance) {
-    const int nrep = md.o_w + 1;
-    std::vector<double> h((size_t)S * md.n_batch * nrep);
+  // [S][kept][C] == per subset C x kept column-major (p.w.predictive.samples)
+  if (o->w_pred_samples && n_test > 0 && !s->tiled)
+    HIPCHK(hipMemcpy(o->w_pred_samples, md.w_pred, (size_t)S * md.n_kept * q * n_test * 8, hipMemcpyDeviceToHost));
+  if (o->acceptance) {   // [S][batch][nrep] -> per subset n_batch x nrep column-major
+    const size_t nb = md.n_batch, nrep = md.o_w + 1;
+    h.resize((size_t)S * nb * nrep);
     HIPCHK(hipMemcpy(h.data(), md.acc_hist, h.size() * 8, hipMemcpyDeviceToHost));
-    for (int i = 0; i < S; ++i)
-      for (int b = 0; b < md.n_batch; ++b)
-        for (int j = 0; j < nrep; ++j)
-          o->acceptance[(size_t)i * md.n_batch * nrep + b + (size_t)j * md.n_batch] =
-              h[((size_t)i * md.n_batch + b) * nrep + j];
+    for (size_t i = 0; i < (size_t)S; ++i)
+      host_layout(o->acceptance + i * nb * nrep, 1, nb, h.data() + i * nb * nrep, (int)nb, (int)nrep, nrep, (int)nb);
   }
   return 0;
 }

@@ -13,9 +13,10 @@ struct ShardInfo {
 };
 int host_error(int code, const char* msg);   // sets mk_last_error()
 int session_info(const mk_session* s, ShardInfo* info);
-int session_param_grids(mk_session* s, double* d_out);                   // [S][P][200]
-int session_wpred_grids(mk_session* s, double* d_out);                   // fused: [S][q n_test][200]
-int session_ppred_grids(mk_session* s, double* d_out);                   // fused: [S][q n_test][200] of p
+// The grid kinds (mk_session_grids' `which`): [S][P][200] of the parameters; of a fused session
+// [S][q n_test][200] of w.predict, or of p = pred_prob(draw) (needs x_test).
+enum GridKind { GRID_PARAMETERS = 0, GRID_W = 1, GRID_P = 2 };
+int session_grids(mk_session* s, GridKind kind, double* d_out);   // into HBM; returns after the stream is idle
 // tiled: [S][q Tc][200]; d_out_p (optional): the p grids of the same replay
 int session_tile_grids(mk_session* s, int t0, double* d_out, mk_outputs* o, double* d_out_p = nullptr);
 // A plain non-blocking stream of the current device from libmk's stream pool, and its return

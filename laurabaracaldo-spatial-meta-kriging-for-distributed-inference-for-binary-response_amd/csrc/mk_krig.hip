@@ -635,24 +635,9 @@ int mk::predict_tiled(mk_session* s, mk_outputs* o) {
     const int Ct = q * std::min(T, n_test - t0);
     int rc = predict_tile(s, t0, grids ? dq : nullptr, o, dqp);
     if (rc) return rc;
-    if (o->p_predict)
-      HIPCHK(hipMemcpy2DAsync(o->p_predict + (size_t)t0 * q * MK_N_LEVELS, (size_t)C * MK_N_LEVELS * 8, dqp,
-                              (size_t)Ct * MK_N_LEVELS * 8, (size_t)Ct * MK_N_LEVELS * 8, S, hipMemcpyDeviceToHost, st));
-    if (o->p_predict_sum) {
-      MK_LAUNCH(k_combine, dim3((unsigned)(((long)Ct * MK_N_LEVELS + 255) / 256)), dim3(256), 0, st, dqp, S,
-                         (long)Ct * MK_N_LEVELS, dsum, 0);
-      HIPCHK(hipMemcpyAsync(o->p_predict_sum + (size_t)t0 * q * MK_N_LEVELS, dsum, (size_t)Ct * MK_N_LEVELS * 8,
-                            hipMemcpyDeviceToHost, st));
-    }
-    if (o->w_predict)   // per subset [C][200]: this tile's columns
-      HIPCHK(hipMemcpy2DAsync(o->w_predict + (size_t)t0 * q * MK_N_LEVELS, (size_t)C * MK_N_LEVELS * 8, dq,
-                              (size_t)Ct * MK_N_LEVELS * 8, (size_t)Ct * MK_N_LEVELS * 8, S, hipMemcpyDeviceToHost, st));
-    if (o->w_predict_sum) {
-      MK_LAUNCH(k_combine, dim3((unsigned)(((long)Ct * MK_N_LEVELS + 255) / 256)), dim3(256), 0, st, dq, S,
-                         (long)Ct * MK_N_LEVELS, dsum, 0);
-      HIPCHK(hipMemcpyAsync(o->w_predict_sum + (size_t)t0 * q * MK_N_LEVELS, dsum, (size_t)Ct * MK_N_LEVELS * 8,
-                            hipMemcpyDeviceToHost, st));
-    }
+    // this tile's columns of every array, p before w; dsum serves both (stream order)
+    if (pgrids && (rc = grids_to_host(s, dqp, Ct, (long)t0 * q, C, o->p_predict, o->p_predict_sum, dsum))) return rc;
+    if (grids && (rc = grids_to_host(s, dq, Ct, (long)t0 * q, C, o->w_predict, o->w_predict_sum, dsum))) return rc;
     HIPCHK(hipStreamSynchronize(st));
   }
   return 0;

@@ -269,11 +269,19 @@ std::string rccl_detail(ncclResult_t e) {
 
 constexpr int L = MK_N_LEVELS;
 
-// The exchange + combine of one grid set: every block's grids [S_r][C][200] are in b.grids (or the
-// buffer `src` names).  Writes (when not NULL) the combined columns: mean (or median) -> h_comb,
-// sum -> h_sum, both 200 x C column-major with column c at c*200.
-int exchange_combine(Node& nd, long C, const mk_combined* comb, double* h_comb, double* h_sum,
-                     DBuf Block::*src = &Block::grids) {
+// One predictive grid kind of the node call: where its outputs go (NULL: not asked for) and which
+// of a block's buffers holds its grids of a tile.
+struct PredKind {
+  GridKind kind;
+  double *h_each, *h_sum, *h_comb;   // per-subset grids, their sequential sum, the combined grid
+  DBuf Block::*tile;
+  bool asked() const { return h_each || h_sum || h_comb; }
+};
+
+// The exchange + combine of one grid set: every block's grids [S_r][C][200] are in its buffer `src`.
+// Writes (when not NULL) the combined columns: mean (or median) -> h_comb, sum -> h_sum, both
+// 200 x C column-major with column c at c*200.
+int exchange_combine(Node& nd, long C, const mk_combined* comb, double* h_comb, double* h_sum, DBuf Block::*src) {
   if (!h_comb && !h_sum) return 0;
   const int G = nd.G, K = nd.K;
   const long per = std::max(1L, (C + G - 1) / G);
@@ -504,58 +512,38 @@ extern "C" int mk_meta_fit(const mk_problem* pr, const mk_config* c, const int32
   });
   if (rc) return rc;
 
-  // ---- parameter grids (MK.R:89) -> out->parameters, combine -> comb->result (MK.R:127)
-  const bool want_par = (out && out->parameters) || (comb && comb->result);
-  if (want_par) {
-    rc = nd.pool->run([&](int r) -> int {
+  // ---- the grids.  A whole grid kind ([S_r][Ck][200] per block, in x.grids): each block's grids to its subsets'
+  // slice of h_each, then the exchange + combine.
+  auto whole_grids = [&](GridKind kind, long Ck, double* h_each, double* h_comb, double* h_sum) -> int {
+    const int failed = nd.pool->run([&](int r) -> int {
       Block& x = *nd.b[r];
       if (!x.ses) return 0;
-      int e = x.grids.ensure((size_t)x.S * P * L);
-      if (e || (e = session_param_grids(x.ses, x.grids.p))) return e;
-      if (out && out->parameters)
-        MHIP(hipMemcpy(out->parameters + (size_t)x.lo * P * L, x.grids.p, (size_t)x.S * P * L * 8, hipMemcpyDeviceToHost));
+      int e = x.grids.ensure((size_t)x.S * Ck * L);
+      if (e || (e = session_grids(x.ses, kind, x.grids.p))) return e;
+      if (h_each) MHIP(hipMemcpy(h_each + (size_t)x.lo * Ck * L, x.grids.p, (size_t)x.S * Ck * L * 8, hipMemcpyDeviceToHost));
       return 0;
     });
-    if (rc) return rc;
-    if (comb && comb->result && (rc = exchange_combine(nd, P, comb, comb->result, nullptr))) return rc;
-  }
+    return failed ? failed : exchange_combine(nd, Ck, comb, h_comb, h_sum, &Block::grids);
+  };
+  // parameter grids (MK.R:89) -> out->parameters, combine -> comb->result (MK.R:127)
+  double* h_par = out ? out->parameters : nullptr;
+  double* h_result = comb ? comb->result : nullptr;
+  if ((h_par || h_result) && (rc = whole_grids(GRID_PARAMETERS, P, h_par, h_result, nullptr))) return rc;
 
   // ---- w.predict grids (MK.R:87-89) -> out->w_predict; combine -> comb->result2 (MK.R:133) and
-  // the sequential sum -> out->w_predict_sum
+  // the sequential sum -> out->w_predict_sum.  p.predict grids -> out->p_predict; combine ->
+  // comb->result3 and the sum -> out->p_predict_sum
   if (n_test > 0) {
-    double* h_w = out ? out->w_predict : nullptr;
-    double* h_sum = out ? out->w_predict_sum : nullptr;
-    double* h_comb = comb ? comb->result2 : nullptr;
-    // p.predict grids -> out->p_predict; combine -> comb->result3 and the sum -> out->p_predict_sum
-    double* h_p = out ? out->p_predict : nullptr;
-    double* h_psum = out ? out->p_predict_sum : nullptr;
-    double* h_pcomb = comb ? comb->result3 : nullptr;
-    const bool want_pg = h_p || h_psum || h_pcomb;
-    const bool want_w = h_w || h_sum || h_comb || (tiled && (want_pg || (out && (out->w_pred_samples || out->p_pred_samples))));
-    if (want_pg && !tiled) {
-      rc = nd.pool->run([&](int r) -> int {
-        Block& x = *nd.b[r];
-        if (!x.ses) return 0;
-        int e = x.grids.ensure((size_t)x.S * C * L);
-        if (e || (e = session_ppred_grids(x.ses, x.grids.p))) return e;
-        if (h_p) MHIP(hipMemcpy(h_p + (size_t)x.lo * C * L, x.grids.p, (size_t)x.S * C * L * 8, hipMemcpyDeviceToHost));
-        return 0;
-      });
-      if (rc) return rc;
-      if ((rc = exchange_combine(nd, C, comb, h_pcomb, h_psum))) return rc;
-    }
-    if (want_w && !tiled) {
-      rc = nd.pool->run([&](int r) -> int {
-        Block& x = *nd.b[r];
-        if (!x.ses) return 0;
-        int e = x.grids.ensure((size_t)x.S * C * L);
-        if (e || (e = session_wpred_grids(x.ses, x.grids.p))) return e;
-        if (h_w) MHIP(hipMemcpy(h_w + (size_t)x.lo * C * L, x.grids.p, (size_t)x.S * C * L * 8, hipMemcpyDeviceToHost));
-        return 0;
-      });
-      if (rc) return rc;
-      if ((rc = exchange_combine(nd, C, comb, h_comb, h_sum))) return rc;
-    } else if (want_w) {
+    const PredKind w{GRID_W, out ? out->w_predict : nullptr, out ? out->w_predict_sum : nullptr,
+                     comb ? comb->result2 : nullptr, &Block::grids};
+    const PredKind pk{GRID_P, out ? out->p_predict : nullptr, out ? out->p_predict_sum : nullptr,
+                      comb ? comb->result3 : nullptr, &Block::grids_p};
+    const bool draws = out && (out->w_pred_samples || out->p_pred_samples);
+    const bool replay = tiled && (w.asked() || pk.asked() || draws);   // one replay per tile serves them all
+    if (!tiled) {
+      for (const PredKind* k : {&pk, &w})   // p before w
+        if (k->asked() && (rc = whole_grids(k->kind, C, k->h_each, k->h_comb, k->h_sum))) return rc;
+    } else if (replay) {
       const int T = info0.pred_tile;
       // every shard replays the same tiles (the exchange combines tile by tile): a shard whose HBM
       // made it take a smaller kriging tile than the others (mk_session_predict_tile) cannot follow
@@ -575,23 +563,18 @@ extern "C" int mk_meta_fit(const mk_problem* pr, const mk_config* c, const int32
           if (!x.ses) return 0;
           mk_outputs o = shard_out(x);
           int e = x.grids.ensure((size_t)x.S * Ct * L);
-          if (!e && want_pg) e = x.grids_p.ensure((size_t)x.S * Ct * L);
-          if (e || (e = session_tile_grids(x.ses, t0, x.grids.p, &o, want_pg ? x.grids_p.p : nullptr))) return e;
-          if (h_p)
-            MHIP(hipMemcpy2D(h_p + (size_t)x.lo * C * L + (size_t)t0 * q * L, (size_t)C * L * 8, x.grids_p.p,
-                             (size_t)Ct * L * 8, (size_t)Ct * L * 8, x.S, hipMemcpyDeviceToHost));
-          if (h_w)   // per subset [C][200]: this tile's columns
-            MHIP(hipMemcpy2D(h_w + (size_t)x.lo * C * L + (size_t)t0 * q * L, (size_t)C * L * 8, x.grids.p,
-                             (size_t)Ct * L * 8, (size_t)Ct * L * 8, x.S, hipMemcpyDeviceToHost));
+          if (!e && pk.asked()) e = x.grids_p.ensure((size_t)x.S * Ct * L);
+          if (e || (e = session_tile_grids(x.ses, t0, x.grids.p, &o, pk.asked() ? x.grids_p.p : nullptr))) return e;
+          for (const PredKind* k : {&w, &pk})   // per subset [C][200]: this tile's columns
+            if (k->h_each)
+              MHIP(hipMemcpy2D(k->h_each + (size_t)x.lo * C * L + (size_t)t0 * q * L, (size_t)C * L * 8, (x.*k->tile).p,
+                               (size_t)Ct * L * 8, (size_t)Ct * L * 8, x.S, hipMemcpyDeviceToHost));
           return 0;
         });
         if (rc) return rc;
-        if ((rc = exchange_combine(nd, Ct, comb, h_comb ? h_comb + (size_t)t0 * q * L : nullptr,
-                                   h_sum ? h_sum + (size_t)t0 * q * L : nullptr)))
-          return rc;
-        if (want_pg && (rc = exchange_combine(nd, Ct, comb, h_pcomb ? h_pcomb + (size_t)t0 * q * L : nullptr,
-                                              h_psum ? h_psum + (size_t)t0 * q * L : nullptr, &Block::grids_p)))
-          return rc;
+        auto at_tile = [&](double* h) { return h ? h + (size_t)t0 * q * L : nullptr; };
+        for (const PredKind* k : {&w, &pk})   // w before p
+          if ((rc = exchange_combine(nd, Ct, comb, at_tile(k->h_comb), at_tile(k->h_sum), k->tile))) return rc;
       }
     }
   }

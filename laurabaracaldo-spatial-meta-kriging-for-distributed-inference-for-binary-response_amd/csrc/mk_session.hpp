@@ -299,6 +299,12 @@ static void timed(mk_session* s, hipStream_t st, int which, double flops, F&& la
 Model model_view(const Model& m, int s0, int S);   // subsets [s0, s0 + S) of the shard's arrays
 MatSet matset_view(const MatSet& m, int s0);
 int setup_groups(mk_session* s, int n_groups);
+// A block of grids [S][Ct][200] in HBM to the host, on the session stream and not waited for: every
+// subset's columns into [col0, col0 + Ct) of its [C][200] array at h_each, and their sequential sum
+// (k_combine into dsum, Ct * 200 doubles) into the same columns of h_sum ([C][200]).  Either host
+// array may be NULL.  A fused session's grids are the block col0 = 0, Ct = C.
+int grids_to_host(mk_session* s, const double* d_grids, long Ct, long col0, long C, double* h_each, double* h_sum,
+                  double* dsum);
 
 // ---- mk_pool.hip
 // A stream of this kind on the current device (hipSetDevice(device) done by the caller), recorded

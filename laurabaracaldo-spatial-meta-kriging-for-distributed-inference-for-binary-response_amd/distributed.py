@@ -138,16 +138,8 @@ def combine_sharded(local, K, dist, method="mean", device=None, gpu=0, combine_f
         for src in range(world):                       # global subset order
             grids += [mine[src, i, :, :b - a] for i in range(counts[src])]
         if combine_fn is None:
-            from .post import combine_median
-            from .session import combine
-            if method == "mean":
-                combine_fn = lambda g: combine(g, device=gpu)                 # noqa: E731
-            elif method == "sum":
-                combine_fn = lambda g: combine(g, device=gpu, mean=False)     # noqa: E731
-            elif method == "median":
-                combine_fn = lambda g: combine_median(g, device=gpu)[0]       # noqa: E731
-            else:
-                raise ValueError(f"error: unknown combine method '{method}'")
+            from .metakriging import combiner
+            combine_fn = combiner(method, gpu)
         buf = torch.zeros((L, cmax), dtype=torch.float64)
         if b > a:
             buf[:, :b - a] = torch.from_numpy(np.ascontiguousarray(combine_fn(grids)))

@@ -122,16 +122,23 @@ def partitioned_spMvGLM(i, y, x, weight, n, q, n_part, coords_test, x_test, inde
                     x_test=x_test)[0]
 
 
+def combiner(method, device=0):
+    """The combine of a list of grids as a function: "mean" (MK.R:123-133, sequential), "sum" (the
+    same without the 1/K) or "median" (Weiszfeld)."""
+    if method == "mean":
+        return lambda grids: combine(grids, device=device)
+    if method == "sum":
+        return lambda grids: combine(grids, device=device, mean=False)
+    if method == "median":
+        return lambda grids: combine_median(grids, device=device)[0]
+    raise ValueError(f"error: unknown combine method '{method}'")
+
+
 def combine_results(obj, device=0, method="mean"):
     """MK.R:123-133: result (200 x P) and result2 (200 x q n_test).  method="median" is the
     Weiszfeld geometric-median extension (the reference averages).
     combine_predictive(obj) gives result3 from the subsets' p.predict grids the same way."""
-    if method == "mean":
-        comb = lambda grids: combine(grids, device=device)             # noqa: E731
-    elif method == "median":
-        comb = lambda grids: combine_median(grids, device=device)[0]   # noqa: E731
-    else:
-        raise ValueError(f"error: unknown combine method '{method}'")
+    comb = combiner(method, device)
     result = comb([o["parameters"] for o in obj])
     result2 = comb([o["w.predict"] for o in obj]) if "w.predict" in obj[0] else None
     return result, result2
@@ -142,11 +149,7 @@ def combine_predictive(obj, device=0, method="mean"):
     w.predict; None when the subsets were fitted without x_test."""
     if "p.predict" not in obj[0]:
         return None
-    if method == "mean":
-        return combine([o["p.predict"] for o in obj], device=device)
-    if method == "median":
-        return combine_median([o["p.predict"] for o in obj], device=device)[0]
-    raise ValueError(f"error: unknown combine method '{method}'")
+    return combiner(method, device)([o["p.predict"] for o in obj])
 
 
 def posterior_summary(result, result2, x_test, q=None, samplesize=1000, seed=20250114, device=0, rng="philox",

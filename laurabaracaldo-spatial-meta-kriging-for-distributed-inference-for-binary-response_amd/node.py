@@ -14,7 +14,8 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from ._lib import Combined, Outputs, check
+from ._lib import Combined, check
+from .outbuf import OutputBuffers
 from .session import PackedProblem
 
 N_LEVELS = _lib.N_LEVELS
@@ -41,41 +42,14 @@ def meta_fit_node(subsets, cfg, coords_test=None, devices=(0,), subset_base=0, m
     devs = np.ascontiguousarray(devices, dtype=np.int32)
     K, P, q, n_test = pp.S, cfg.P, cfg.q, pp.n_test
     C = q * n_test
-    res = {}
-    o = Outputs()
-    if per_subset:
-        res["parameters"] = np.zeros((K, P, N_LEVELS))
-        o.parameters = _lib.dptr(res["parameters"])
-        if n_test:
-            res["w_predict"] = np.zeros((K, C, N_LEVELS))
-            o.w_predict = _lib.dptr(res["w_predict"])
-    if samples:
-        res["samples"] = np.zeros((K, P, cfg.n_samples))
-        o.samples = _lib.dptr(res["samples"])
-    if w_samples:
-        res["_w"] = np.zeros(int(pp.n_part.sum()) * q * cfg.n_samples)
-        o.w_samples = _lib.dptr(res["_w"])
-    if w_pred_samples and n_test:
-        res["w_pred_samples"] = np.zeros((K, cfg.kept, C))
-        o.w_pred_samples = _lib.dptr(res["w_pred_samples"])
-    if acceptance:
-        res["acceptance"] = np.zeros((K, cfg.p + cfg.n_theta + 1, cfg.n_batch))
-        o.acceptance = _lib.dptr(res["acceptance"])
-    if w_predict_sum and n_test:
-        res["w_predict_sum"] = np.zeros((C, N_LEVELS))
-        o.w_predict_sum = _lib.dptr(res["w_predict_sum"])
-    have_x = pp.x_test is not None and n_test > 0
+    have = n_test > 0
+    have_x = pp.x_test is not None and have
     if (p_pred_samples or p_predict_sum) and not have_x:
         raise ValueError("error: p_pred_samples / p_predict_sum need x_test")
-    if have_x and per_subset:
-        res["p_predict"] = np.zeros((K, C, N_LEVELS))
-        o.p_predict = _lib.dptr(res["p_predict"])
-    if p_pred_samples:
-        res["p_pred_samples"] = np.zeros((K, cfg.kept, C))
-        o.p_pred_samples = _lib.dptr(res["p_pred_samples"])
-    if p_predict_sum:
-        res["p_predict_sum"] = np.zeros((C, N_LEVELS))
-        o.p_predict_sum = _lib.dptr(res["p_predict_sum"])
+    on = dict(parameters=per_subset, w_predict=per_subset and have, samples=samples, w_samples=w_samples,
+              w_pred_samples=w_pred_samples and have, acceptance=acceptance, w_predict_sum=w_predict_sum and have,
+              p_predict=per_subset and have_x, p_pred_samples=p_pred_samples, p_predict_sum=p_predict_sum)
+    ob = OutputBuffers(K, cfg, pp.n_part, n_test, cfg.kept, {f for f, v in on.items() if v})
     cb = Combined()
     result = np.zeros((P, N_LEVELS))
     cb.result = _lib.dptr(result)
@@ -94,34 +68,11 @@ def meta_fit_node(subsets, cfg, coords_test=None, devices=(0,), subset_base=0, m
 
     fn = _lib.PROGRESS_FN(_cb)
     check(lib.mk_meta_fit(ctypes.byref(pp.c), ctypes.byref(c), devs.ctypes.data_as(_lib._ip), len(devs), fn, None,
-                          ctypes.byref(o), ctypes.byref(cb)))
+                          ctypes.byref(ob.c), ctypes.byref(cb)))
     del keep
     out = {"result": result.T.copy(), "result2": None if result2 is None else result2.T.copy(),
            "exchange": "rccl" if cb.exchange else "copy", "comm_ranks": int(cb.comm_ranks)}
     if result3 is not None:
         out["result3"] = result3.T.copy()
-    for k in ("p_predict", "p_pred_samples"):
-        if k in res:
-            out[k] = [res[k][i].T.copy() for i in range(K)]
-    if "p_predict_sum" in res:
-        out["p_predict_sum"] = res["p_predict_sum"].T.copy()
-    if "parameters" in res:
-        out["parameters"] = [res["parameters"][i].T.copy() for i in range(K)]
-    if "w_predict" in res:
-        out["w_predict"] = [res["w_predict"][i].T.copy() for i in range(K)]
-    if "samples" in res:
-        out["samples"] = [res["samples"][i].T.copy() for i in range(K)]
-    if "_w" in res:
-        flat, off, ws = res["_w"], 0, []
-        for ns in pp.n_part:
-            N = int(ns) * q
-            ws.append(flat[off:off + N * cfg.n_samples].reshape(cfg.n_samples, N).T.copy())
-            off += N * cfg.n_samples
-        out["w_samples"] = ws
-    if "w_pred_samples" in res:
-        out["w_pred_samples"] = [res["w_pred_samples"][i].T.copy() for i in range(K)]
-    if "acceptance" in res:
-        out["acceptance"] = [res["acceptance"][i].T.copy() for i in range(K)]
-    if "w_predict_sum" in res:
-        out["w_predict_sum"] = res["w_predict_sum"].T.copy()
+    out.update(ob.unpack())
     return out

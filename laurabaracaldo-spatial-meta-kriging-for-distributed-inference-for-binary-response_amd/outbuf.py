@@ -1,0 +1,56 @@
+"""The host arrays behind an mk_outputs (include/mk.h) and their way back to the caller's layouts:
+one table of field -> shape serves Session.outputs and meta_fit_node."""
+import numpy as np
+
+from ._lib import N_LEVELS, Outputs, dptr
+
+# The array libmk fills for each mk_outputs field, row-major, in terms of: K subsets, P parameters,
+# C = q n_test kriging columns, L levels, n = n_samples, kept states, B amcmc batches, R = P + 1
+# acceptance rows, W = sum_i n_part[i] q n (the ragged w samples, flat).  R's column-major matrix is
+# the transpose of the trailing two axes: per subset (K first), or one matrix (the sums).
+SHAPES = {
+    "parameters": ("K", "P", "L"),            # -> K x (200 x P)
+    "w_predict": ("K", "C", "L"),             # -> K x (200 x q n_test)
+    "samples": ("K", "P", "n"),               # -> K x (n_samples x P)
+    "w_samples": ("W",),                      # -> subset i: (n_part[i] q) x n_samples
+    "w_pred_samples": ("K", "kept", "C"),     # -> K x ((q n_test) x kept)
+    "acceptance": ("K", "R", "B"),            # -> K x (n_batch x R)
+    "w_predict_sum": ("C", "L"),              # -> 200 x q n_test
+    "p_predict": ("K", "C", "L"),
+    "p_pred_samples": ("K", "kept", "C"),
+    "p_predict_sum": ("C", "L"),
+}
+
+
+class OutputBuffers:
+    """Arrays for the requested `fields` of K subsets (n_part sites each), `kept` states per draw
+    array: `.c` is the mk_outputs pointing at them, `.buf[field]` the arrays, and unpack() -- after
+    the library call -- the dict Session.outputs documents."""
+
+    def __init__(self, K, cfg, n_part, n_test, kept, fields):
+        unknown = set(fields) - set(SHAPES)
+        if unknown:
+            raise KeyError(f"unknown output fields {sorted(unknown)}")
+        self.K, self.q, self.n_samples = int(K), cfg.q, cfg.n_samples
+        self.n_part = [int(ns) for ns in n_part]
+        dims = dict(K=self.K, P=cfg.P, C=cfg.q * int(n_test), L=N_LEVELS, n=cfg.n_samples, kept=int(kept),
+                    B=cfg.n_batch, R=cfg.P + 1, W=sum(self.n_part) * cfg.q * cfg.n_samples)
+        self.buf = {f: np.zeros(tuple(dims[d] for d in shape)) for f, shape in SHAPES.items() if f in fields}
+        self.c = Outputs()
+        for f, a in self.buf.items():
+            setattr(self.c, f, dptr(a))
+
+    def _unpack(self, a):
+        if a.ndim == 3:
+            return [a[i].T.copy() for i in range(self.K)]
+        if a.ndim == 2:
+            return a.T.copy()
+        out, off = [], 0
+        for ns in self.n_part:                                # the ragged w samples
+            N = ns * self.q
+            out.append(a[off:off + N * self.n_samples].reshape(self.n_samples, N).T.copy())
+            off += N * self.n_samples
+        return out
+
+    def unpack(self):
+        return {f: self._unpack(a) for f, a in self.buf.items()}

@@ -9,7 +9,8 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from ._lib import Config, Outputs, Problem, check, dptr, iptr
+from ._lib import Config, Problem, check, dptr, iptr
+from .outbuf import OutputBuffers
 
 COV_MODELS = {"exponential": _lib.MK_COV_EXPONENTIAL, "matern": _lib.MK_COV_MATERN}
 LINKS = {"logit": _lib.MK_LINK_LOGIT, "probit": _lib.MK_LINK_PROBIT}
@@ -180,6 +181,7 @@ class Session:
         check(lib.mk_session_create(ctypes.byref(pr), ctypes.byref(c), ctypes.byref(h)))
         self._h = h
         self._lib = lib
+        self._window = None     # kept states of the next outputs(), once set_kept_window narrowed them
         if lookahead is not None:
             self.set_lookahead(lookahead)
 
@@ -295,75 +297,17 @@ class Session:
         p_predict / p_pred_samples / p_predict_sum: the same three of p(y = 1) = linkinv(x.test beta + w)
         per kept state (they need x_test); p_predict defaults to on when quantiles is and the session has
         covariates."""
-        cfg = self.cfg
-        S, P, q = self.S, cfg.P, cfg.q
-        o = Outputs()
-        res = {}
+        have = bool(self.n_test)       # the w outputs are simply absent without test sites
         if p_predict is None:
-            p_predict = bool(quantiles) and self.x_test is not None and bool(self.n_test)
-        kept = getattr(self, "_window", cfg.kept)
-        C = q * self.n_test
-        if p_predict:
-            res["p_predict"] = np.zeros((S, C, _lib.N_LEVELS))
-            o.p_predict = dptr(res["p_predict"])
-        if p_pred_samples:
-            res["p_pred_samples"] = np.zeros((S, kept, C))
-            o.p_pred_samples = dptr(res["p_pred_samples"])
-        if p_predict_sum:
-            res["p_predict_sum"] = np.zeros((C, _lib.N_LEVELS))
-            o.p_predict_sum = dptr(res["p_predict_sum"])
-        if quantiles:
-            res["parameters"] = np.zeros((S, P, _lib.N_LEVELS))
-            o.parameters = dptr(res["parameters"])
-            if self.n_test and w_predict:
-                res["w_predict"] = np.zeros((S, q * self.n_test, _lib.N_LEVELS))
-                o.w_predict = dptr(res["w_predict"])
-        if samples:
-            res["samples"] = np.zeros((S, P, cfg.n_samples))
-            o.samples = dptr(res["samples"])
-        if w_samples:
-            tot = int(self.n_part.sum()) * q * cfg.n_samples
-            res["_w_samples_flat"] = np.zeros(tot)
-            o.w_samples = dptr(res["_w_samples_flat"])
-        if w_pred_samples and self.n_test:
-            res["w_pred_samples"] = np.zeros((S, getattr(self, "_window", cfg.kept), q * self.n_test))
-            o.w_pred_samples = dptr(res["w_pred_samples"])
-        if acceptance:
-            nrep = cfg.p + cfg.n_theta + 1
-            res["acceptance"] = np.zeros((S, nrep, cfg.n_batch))
-            o.acceptance = dptr(res["acceptance"])
-        if w_predict_sum and self.n_test:
-            res["w_predict_sum"] = np.zeros((q * self.n_test, _lib.N_LEVELS))
-            o.w_predict_sum = dptr(res["w_predict_sum"])
-        check(self._lib.mk_session_outputs(self._h, ctypes.byref(o)))
-        out = {}
-        # device/R layout: per subset column-major (levels x cols) == row-major (cols, levels)
-        if "parameters" in res:
-            out["parameters"] = [res["parameters"][i].T.copy() for i in range(S)]          # 200 x P
-        if "w_predict" in res:
-            out["w_predict"] = [res["w_predict"][i].T.copy() for i in range(S)]            # 200 x q*n_test
-        if "samples" in res:
-            out["samples"] = [res["samples"][i].T.copy() for i in range(S)]                # n_samples x P
-        if "_w_samples_flat" in res:
-            flat, off, ws = res["_w_samples_flat"], 0, []
-            for ns in self.n_part:
-                N = int(ns) * q
-                ws.append(flat[off:off + N * cfg.n_samples].reshape(cfg.n_samples, N).T.copy())   # N x n_samples
-                off += N * cfg.n_samples
-            out["w_samples"] = ws
-        if "w_pred_samples" in res:
-            out["w_pred_samples"] = [res["w_pred_samples"][i].T.copy() for i in range(S)]  # (q n_test) x kept
-        if "w_predict_sum" in res:
-            out["w_predict_sum"] = res["w_predict_sum"].T.copy()                               # 200 x q*n_test
-        if "p_predict" in res:
-            out["p_predict"] = [res["p_predict"][i].T.copy() for i in range(S)]            # 200 x q*n_test
-        if "p_pred_samples" in res:
-            out["p_pred_samples"] = [res["p_pred_samples"][i].T.copy() for i in range(S)]  # (q n_test) x kept
-        if "p_predict_sum" in res:
-            out["p_predict_sum"] = res["p_predict_sum"].T.copy()                               # 200 x q*n_test
-        if "acceptance" in res:
-            out["acceptance"] = [res["acceptance"][i].T.copy() for i in range(S)]          # n_batch x nrep
-        return out
+            p_predict = bool(quantiles) and self.x_test is not None and have
+        on = dict(parameters=quantiles, w_predict=quantiles and w_predict and have, samples=samples,
+                  w_samples=w_samples, w_pred_samples=w_pred_samples and have, acceptance=acceptance,
+                  w_predict_sum=w_predict_sum and have, p_predict=p_predict, p_pred_samples=p_pred_samples,
+                  p_predict_sum=p_predict_sum)
+        kept = self.cfg.kept if self._window is None else self._window
+        ob = OutputBuffers(self.S, self.cfg, self.n_part, self.n_test, kept, {f for f, v in on.items() if v})
+        check(self._lib.mk_session_outputs(self._h, ctypes.byref(ob.c)))
+        return ob.unpack()
 
     def close(self):
         if getattr(self, "_h", None):

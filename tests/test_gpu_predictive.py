@@ -285,3 +285,47 @@ def test_errors_leave_the_session_usable(mk):
         h = ctypes.c_void_p()
         mk._lib.check(lib.mk_session_create(ctypes.byref(pr.c), ctypes.byref(c), ctypes.byref(h)))
     assert e.value.code == mk._lib.MK_E_ARG
+
+
+_ALL = dict(samples=True, w_samples=True, w_pred_samples=True, acceptance=True, w_predict_sum=True, p_predict=True,
+            p_pred_samples=True, p_predict_sum=True)
+# Session.outputs arguments that ask for one field (quantiles=True brings parameters with w_predict)
+_ALONE = dict(parameters=dict(w_predict=False, p_predict=False), w_predict=dict(p_predict=False),
+              p_predict=dict(quantiles=False, p_predict=True),
+              **{k: {"quantiles": False, k: True} for k in _ALL if k != "p_predict"})
+
+
+def _assert_same(a, b, what):
+    if isinstance(a, list):
+        assert len(a) == len(b), what
+        for s, (x, y) in enumerate(zip(a, b)):
+            assert x.shape == y.shape and np.array_equal(x, y), (what, s)
+    else:
+        assert a.shape == b.shape and np.array_equal(a, b), what
+
+
+@pytest.mark.parametrize("tile", [0, 4])
+def test_every_field_at_once_equals_each_alone(mk, tile):
+    """Ragged subsets (37 / 64 / 50 sites), q = 2, 9 test sites, fused and in tiles of 4, 4 and 1
+    sites: one outputs() call with every field on gives, field by field, the arrays of a call that
+    asks for that field alone (both grid kinds share one call's scratch), and the node driver over
+    two blocks of one device gives the session's arrays, its result2 / result3 the sequential mean
+    of the per-subset grids."""
+    d, subs = _problem(mk, [37, 64, 50], 2)
+    ct, xt = d["coords_test"][:9], d["x_test"][:18]
+    cfg = _cfg(mk, 2, predict_tile=tile, n_batch=4, batch_length=5)
+    with mk.Session(subs, cfg, coords_test=ct, x_test=xt, record_w=True) as ses:
+        ses.run(cfg.n_samples)
+        assert ses.predict_tile == tile
+        every = ses.outputs(**_ALL)
+        assert set(every) == set(_ALONE)
+        for field, kw in _ALONE.items():
+            _assert_same(ses.outputs(**kw)[field], every[field], field)
+    assert every["p_predict"][2].shape == (200, 18) and every["w_samples"][1].shape == (128, 20)
+    node_kw = {k: v for k, v in _ALL.items() if k != "p_predict"}
+    got = mk.meta_fit_node(subs, cfg, coords_test=ct, devices=[0, 0], x_test=xt, **node_kw)
+    for field in ("parameters", "w_predict", "p_predict", "w_pred_samples", "p_pred_samples", "w_predict_sum",
+                  "p_predict_sum"):
+        _assert_same(got[field], every[field], "node " + field)
+    assert np.array_equal(got["result2"], mk.combine(every["w_predict"]))
+    assert np.array_equal(got["result3"], mk.combine(every["p_predict"]))
