@@ -107,9 +107,7 @@ __device__ inline double frag(const double* img, int m, int k) {
 // outputs nobody reads, so results are unchanged and the SIMD's matrix pipe goes to the
 // co-resident wave instead).  Block indices are absolute within the 128-tile (rb0 / cb0: the
 // sub-tile's offset in 16-blocks), so a sub-tile skips exactly what its 128-tile would:
-//   SKIP_UPPER  output tile on the diagonal of a symmetric update: 16-blocks above the
-//               diagonal (column block > row block) are never read   (flag = tile is diagonal)
-//   SKIP_TRI_B  op(B) lower-triangular in (n, k) over one 128-deep K: chunk c only touches
+//   SKIP_TRI_B op(B) lower-triangular in (n, k) over one 128-deep K: chunk c only touches
 //               output column blocks >= c                             (flag = chunk index c)
 //   SKIP_TRI_A  op(A) lower-triangular in (m, k) over the 128-deep K block starting at diag_tile
 //               (gemm_tile): chunk c' of that block only touches output row blocks >= c'
@@ -117,7 +115,9 @@ __device__ inline double frag(const double* img, int m, int k) {
 //   SKIP_TRI_BL op(B) lower-triangular in (k, n) over the 128-deep K block starting at diag_tile:
 //               chunk c' of that block only touches output column blocks <= c'
 //               (flag = c' inside the block, SKIP_FLAG_NONE elsewhere)
-enum { SKIP_NONE = 0, SKIP_UPPER = 1, SKIP_TRI_B = 2, SKIP_TRI_A = 3, SKIP_TRI_BL = 4 };
+// (A diagonal tile's unread upper 16-blocks are not a skip of this body -- a predicate here leaves
+// wave (1,0) with all 16 of its blocks -- but a body of their own: gemm_syrk_128 below.)
+enum { SKIP_NONE = 0, SKIP_TRI_B = 2, SKIP_TRI_A = 3, SKIP_TRI_BL = 4 };
 constexpr int SKIP_FLAG_NONE = 1 << 20;
 
 // MASK: fragments with chunk-relative k >= kvalid read as zero.
@@ -144,7 +144,6 @@ __device__ inline void mma_chunk(const double* As, const double* Bs, AccT<TM / 3
     for (int bm = 0; bm < BM; ++bm)
 #pragma unroll
       for (int bn = 0; bn < BN; ++bn) {
-        if (SKIP == SKIP_UPPER && flag && cb0 + wn * BN + bn > rb0 + wm * BM + bm) continue;
         if (SKIP == SKIP_TRI_B && flag > cb0 + wn * BN + bn) continue;
         if (SKIP == SKIP_TRI_A && flag > rb0 + wm * BM + bm) continue;
         if (SKIP == SKIP_TRI_BL && flag < cb0 + wn * BN + bn) continue;
@@ -159,7 +158,7 @@ __device__ inline void mma_chunk(const double* As, const double* Bs, AccT<TM / 3
 // (triangular operands) then stream the same chunks at the same time, so an XCD's L2
 // serves the shared panels once.  SAME: op(B) = op(A)^T read from the same memory (A'A
 // products, TM == TN): one DMA and one LDS image serve both fragments.
-// SKIP (see mma_chunk): SKIP_UPPER with diag_tile != 0; SKIP_TRI_B for K = 128; SKIP_TRI_A /
+// SKIP (see mma_chunk): SKIP_TRI_B for K = 128; SKIP_TRI_A /
 // SKIP_TRI_BL with diag_tile = the K offset of the triangular 128-deep block.
 // lds: gb_lds_bytes(TM, TN) of dynamic LDS.  Ends with a barrier (the caller may reuse the LDS).
 template <int TM, int TN, bool A_MU, bool B_NU, bool NEG = false, bool REV = false, bool SAME = false,
@@ -342,6 +341,134 @@ __device__ inline void store_tile(double* C, long ldc, const AccT<BM, BN>& acc, 
         C[m + (long)n * ldc] = acc.v[bm][bn][r];
         if (Ct) Ct[n + (long)m * ldc] = acc.v[bm][bn][r];
       }
+}
+
+// ---------------------------------------------------------------- symmetric rank-K update, lower 16-blocks only
+// acc -= P P^T for a 128 x K panel P (m-contiguous: op(P)(m, k) = P[m + k*s]) -- the diagonal
+// tiles' update, of which only the lower triangle is ever read.  The 36 16-blocks with cb <= rb
+// are dealt evenly: wave w owns row blocks w and 7 - w, nine blocks,
+//   slot s <= w : block (rb = w,     cb = s)
+//   slot s >  w : block (rb = 7 - w, cb = s - w - 1)
+// so every wave issues 9 MFMAs per k-step where the quadrant body issues 16 (a skip inside that
+// body leaves wave (1,0) with all 16 of its blocks: the workgroup is no shorter), one LDS image
+// serves both fragments (half the DMA bytes of two), and no predicate sits in the K loop.  Blocks on
+// the diagonal are computed whole.  Slots are indexed statically; rb and cb are wave-uniform scalars
+// that only enter LDS and memory addresses.
+// Per element the MFMA sequence is mma_chunk's (ascending 16-deep chunks, four k-steps with
+// k = 4 ks + (lane >> 4), first operand the column block's fragment, second the negated row
+// block's), so every lower-triangle element has the bits gemm_tile<128, 128, true, true, true>
+// gives it.  Accumulator: lane l, register r of slot s is C[16 rb + (l & 15)][16 cb + (l >> 4) + 4r].
+constexpr int SYRK_SLOTS = 9;
+__host__ __device__ constexpr int syrk_rb(int w, int s) { return s <= w ? w : 7 - w; }
+__host__ __device__ constexpr int syrk_cb(int w, int s) { return s <= w ? s : s - w - 1; }
+// every block with cb <= rb exactly once, nothing else
+constexpr bool syrk_cover_exact() {
+  int cnt[8][8] = {};
+  for (int w = 0; w < 4; ++w)
+    for (int s = 0; s < SYRK_SLOTS; ++s) {
+      const int rb = syrk_rb(w, s), cb = syrk_cb(w, s);
+      if (rb < 0 || rb > 7 || cb < 0 || cb > rb) return false;
+      ++cnt[rb][cb];
+    }
+  for (int rb = 0; rb < 8; ++rb)
+    for (int cb = 0; cb < 8; ++cb)
+      if (cnt[rb][cb] != (cb <= rb ? 1 : 0)) return false;
+  return true;
+}
+static_assert(syrk_cover_exact(), "the SYRK block map covers the lower 16-blocks exactly once");
+// what mma_chunk_syrk relies on: slot 0 is in row block w and slots 4.. in row block 7 - w for every
+// wave, and the last slot is the second row block's diagonal block
+constexpr bool syrk_rows_static() {
+  for (int w = 0; w < 4; ++w) {
+    if (syrk_rb(w, 0) != w || syrk_cb(w, SYRK_SLOTS - 1) != 7 - w) return false;
+    for (int s = 4; s < SYRK_SLOTS; ++s)
+      if (syrk_rb(w, s) != 7 - w) return false;
+  }
+  return true;
+}
+static_assert(syrk_rows_static(), "slot 0 / slots 4.. have the same row choice on every wave");
+
+struct AccSyrk {
+  d4 v[SYRK_SLOTS];
+};
+__device__ inline int syrk_wave() { return __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)); }
+// Element coordinates of accumulator (s, r) for this lane (within the 128 x 128 tile).
+__device__ inline int syrk_row(int w, int s) { return 16 * syrk_rb(w, s) + (threadIdx.x & 15); }
+__device__ inline int syrk_col(int w, int s, int r) { return 16 * syrk_cb(w, s) + ((threadIdx.x & 63) >> 4) + 4 * r; }
+
+__device__ inline void mma_chunk_syrk(const double* Ps, AccSyrk& acc, int w) {
+  constexpr int LD = gb_stride(128);
+  const int lane = threadIdx.x & 63;
+  const int li = lane & 15, lk = lane >> 4;
+#pragma unroll
+  for (int ks = 0; ks < GB_K / 4; ++ks) {
+    const double* row = Ps + (ks * 4 + lk) * LD + li;
+    // the two row blocks' fragments; the second is also the last slot's column fragment
+    const double p0 = row[16 * w], p1 = row[16 * (7 - w)];
+    const double y0 = -p0, y1 = -p1;
+    double xb[SYRK_SLOTS];
+#pragma unroll
+    for (int s = 0; s < SYRK_SLOTS - 1; ++s) xb[s] = row[16 * syrk_cb(w, s)];
+    xb[SYRK_SLOTS - 1] = p1;
+#pragma unroll
+    for (int s = 0; s < SYRK_SLOTS; ++s) {
+      const double ya = s == 0 ? y0 : (s >= 4 ? y1 : (s <= w ? y0 : y1));   // a wave-uniform select
+      acc.v[s] = __builtin_amdgcn_mfma_f64_16x16x4f64(xb[s], ya, acc.v[s], 0, 0, 0);
+    }
+  }
+}
+
+// K % GB_K == 0.  lds: 2 * gb_img(128) doubles (two stages of the one image).  Ends with a barrier
+// (the caller may reuse the LDS).
+__device__ inline void gemm_syrk_128(const double* __restrict__ P, long s, int K, AccSyrk& acc, double* lds) {
+  constexpr int STAGE = gb_img(128);
+  if (K <= 0) return;
+  const int nch = K / GB_K;
+  const int w = syrk_wave();
+  dma_chunk<true, 128>(P, s, 0, lds);
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  for (int c = 0; c < nch; ++c) {
+    // the stage chunk c+1 overwrites was last read in iteration c-1, which every wave has left
+    if (c + 1 < nch) dma_chunk<true, 128>(P, s, GB_K * (c + 1), lds + ((c + 1) & 1) * STAGE);
+    mma_chunk_syrk(lds + (c & 1) * STAGE, acc, w);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+  }
+}
+
+// acc = the nine blocks of C (column-major, ldc); C = acc.
+__device__ inline void acc_load_syrk(AccSyrk& acc, const double* C, long ldc) {
+  const int w = syrk_wave();
+#pragma unroll
+  for (int s = 0; s < SYRK_SLOTS; ++s)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) acc.v[s][r] = C[syrk_row(w, s) + (long)syrk_col(w, s, r) * ldc];
+}
+__device__ inline void store_tile_syrk(double* C, long ldc, const AccSyrk& acc) {
+  const int w = syrk_wave();
+#pragma unroll
+  for (int s = 0; s < SYRK_SLOTS; ++s)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) C[syrk_row(w, s) + (long)syrk_col(w, s, r) * ldc] = acc.v[s][r];
+}
+// The store into a column-major LDS image T (stride tld) that holds the lower triangle and zeros
+// above it: elements above the diagonal inside the diagonal blocks are masked, and all 256 threads
+// zero the 28 blocks with cb > rb (one element of each per thread).
+__device__ inline void store_tile_syrk_lds(double* T, int tld, const AccSyrk& acc) {
+  const int w = syrk_wave();
+#pragma unroll
+  for (int s = 0; s < SYRK_SLOTS; ++s)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int rr = syrk_row(w, s), cc = syrk_col(w, s, r);
+      T[rr + cc * tld] = rr >= cc ? acc.v[s][r] : 0.0;
+    }
+  const int zr = threadIdx.x & 15, zc = threadIdx.x >> 4;
+#pragma unroll
+  for (int rb = 0; rb < 8; ++rb)
+#pragma unroll
+    for (int cb = rb + 1; cb < 8; ++cb) T[(16 * rb + zr) + (16 * cb + zc) * tld] = 0.0;
 }
 
 }  // namespace mk

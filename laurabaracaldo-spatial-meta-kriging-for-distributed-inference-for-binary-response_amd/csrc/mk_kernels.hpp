@@ -15,16 +15,16 @@ inline CovCandidateKernel cov_candidate_kernel(int model) {
 }
 template <int TM, int TN = TM>
 __global__ void k_chol_update(MatSet ms, int S, int h0, int hc, int k, int ia, int ib, int j0, int j1,
-                              const int* slist, const int* scount);
+                              const int* slist, const int* scount, int syrk);
 template <int TM>
 __global__ void k_chol_trsm(MatSet ms, int S, int h0, int hc, int k, int ia, int ib, const int* slist,
                             const int* scount);
 int pv_grid(int max_entries, int nt, int ntt);   // k_pred_var's grid (mk_linalg.hip)
 template <int TM>
 __global__ void k_chol_update_trsm(MatSet ms, int S, int h0, int hc, int k, int ia, int ib, int j0, int extra,
-                                   const int* slist, const int* scount);
+                                   const int* slist, const int* scount, int syrk);
 __global__ void k_chol_diag(MatSet ms, const int* n_s, int h0, int hc, int k, double* ld_part, double* quad_c, int* info,
-                            const int* slist, const int* scount, int cj0, int cj1);
+                            const int* slist, const int* scount, int cj0, int cj1, int syrk);
 __global__ void k_inv_copydiag(MatSet ms, const int* list, const int* count);
 template <int TM>
 __global__ void k_inv_level(MatSet ms, const int* list, const int* count, int sz, int phase);

@@ -305,7 +305,7 @@ __global__ __launch_bounds__(256) void k_cand_border(Model md, MatSet ms, int h0
 // so every element sees the same MFMA sequence as one [0, k) launch (same bits).
 template <int TM, int TN>
 __global__ __launch_bounds__(256, 2) void k_chol_update(MatSet ms, int S, int h0, int hc, int k, int ia, int ib,
-                                                       int j0, int j1, const int* slist, const int* scount) {
+                                                       int j0, int j1, const int* slist, const int* scount, int syrk) {
   extern __shared__ __attribute__((aligned(16))) double lds[];   // gb_lds_bytes(TM, TN) (two DMA stages)
   constexpr int SUBR = MK_NB / TM, SUB = SUBR * (MK_NB / TN);
   const int ntk = ib - ia;
@@ -321,17 +321,28 @@ __global__ __launch_bounds__(256, 2) void k_chol_update(MatSet ms, int S, int h0
   double* M = mat_slot(ms, sh, 1 - ms.cur[sh]);
   const long ld = ms.ld;
   double* C = M + i * MK_NB + sr * TM + (long)(k * MK_NB + sc * TN) * ld;
+  const long jo = (long)j0 * MK_NB * ld;
+  // The 128-tile on the diagonal: the balanced lower-block body (gemm_syrk_128; syrk = 0: the full
+  // square).  (Skipping the unused upper quadrant inside the quadrant body -- per MFMA or per chunk --
+  // measured slower: wave (1,0) keeps all 16 of its blocks, so the workgroup is no shorter and the
+  // predicate sits in the K loop.  The balanced map gives every wave 9 blocks and needs none.)  The
+  // sub-tile instances keep the quadrant body: the independent form the MK_TILE runs compare with.
+  if (TM == 128 && TN == 128 && i == k && syrk) {
+    AccSyrk a;
+    acc_load_syrk(a, C, ld);
+    gemm_syrk_128(M + i * MK_NB + jo, ld, (j1 - j0) * MK_NB, a, lds);
+    store_tile_syrk(C, ld, a);
+    return;
+  }
   AccT<TM / 32, TN / 32> acc;
   acc_load(acc, C, ld);
-  // (Skipping the diagonal tiles' unused upper quadrant -- per MFMA or per chunk -- measured slower.)
-  const long jo = (long)j0 * MK_NB * ld;
   gemm_tile<TM, TN, true, true, true>(M + i * MK_NB + sr * TM + jo, ld, M + k * MK_NB + sc * TN + jo, ld,
                                       (j1 - j0) * MK_NB, (j1 - j0) * MK_NB, acc, lds);
   store_tile(C, ld, acc);
 }
-template __global__ void k_chol_update<128, 128>(MatSet, int, int, int, int, int, int, int, int, const int*, const int*);
-template __global__ void k_chol_update<64, 64>(MatSet, int, int, int, int, int, int, int, int, const int*, const int*);
-template __global__ void k_chol_update<32, 32>(MatSet, int, int, int, int, int, int, int, int, const int*, const int*);
+template __global__ void k_chol_update<128, 128>(MatSet, int, int, int, int, int, int, int, int, const int*, const int*, int);
+template __global__ void k_chol_update<64, 64>(MatSet, int, int, int, int, int, int, int, int, const int*, const int*, int);
+template __global__ void k_chol_update<32, 32>(MatSet, int, int, int, int, int, int, int, int, const int*, const int*, int);
 
 // TM = 64: the tile's two row halves on two workgroups (in place: each reads and writes its own
 // rows only), bit-identical.
@@ -373,8 +384,9 @@ template __global__ void k_chol_trsm<32>(MatSet, int, int, int, int, int, int, c
 //     in order from zero, the same fragment values) -- C(i,k) never goes through HBM between the
 //     two, and every wave solves its own rows: the same triangular work on all four SIMDs;
 //   job t = ntk * 128/TM (extra = 1, sequential schedule): the next diagonal tile's update by
-//     panels [0, k), stored partial; its correction by panel k (k_chol_update, accumulator from
-//     memory) follows the launch, then its factor.
+//     panels [0, k), stored partial (syrk: lower 16-blocks only, gemm_syrk_128 -- the tile's upper
+//     blocks in memory are not touched; syrk = 0: the full square); its correction by panel k
+//     (accumulator from memory) follows the launch, then its factor.
 // Winv_k exists before the launch starts.  Same per-element sequences as U(k), T(k): same bits
 // (tests/test_gpu_linalg.py).
 // Epilogue: the accumulator's block (bm, c), k-step r is chunk c's A fragment, in registers; the
@@ -382,12 +394,20 @@ template __global__ void k_chol_trsm<32>(MatSet, int, int, int, int, int, int, c
 // workgroups per CU).
 template <int TM>
 __global__ __launch_bounds__(256, 2) void k_chol_update_trsm(MatSet ms, int S, int h0, int hc, int k, int ia, int ib,
-                                                            int j0, int extra, const int* slist, const int* scount) {
+                                                            int j0, int extra, const int* slist, const int* scount,
+                                                            int syrk) {
   extern __shared__ __attribute__((aligned(16))) double lds[];   // gb_lds_bytes(128, 128)
   constexpr int SUB = MK_NB / TM, BM = TM / 64;
   const int ntk = ib - ia;
   int e, t, s, h;
-  if (!xcd_map(active_pairs(slist, scount, S, hc), ntk * SUB + extra, &e, &t) ||
+  // syrk: the extra jobs are 9/16 as long as the row jobs, and dealt among them (each matrix's last
+  // item) they made the launch slower, not faster -- a slot they free early takes the next row job
+  // beside a running one, and the launch ends with row jobs doubled up on some CUs while others idle
+  // (launches with an odd job count per matrix: 683 -> 787, 958 -> 1044 us).  Dealt after every row
+  // job of their XCD (xcd_map_tail) they fill the last wave instead (475 -> 400 us with two jobs per
+  // matrix, 821 -> 774 with four, 683 -> 673 with three).
+  const int E = active_pairs(slist, scount, S, hc);
+  if (!((extra && syrk) ? xcd_map_tail(E, ntk * SUB + extra, &e, &t) : xcd_map(E, ntk * SUB + extra, &e, &t)) ||
       !pick_pair(slist, scount, e, h0, hc, &s, &h))
     return;
   const int sh = s * ms.q + h;
@@ -396,6 +416,13 @@ __global__ __launch_bounds__(256, 2) void k_chol_update_trsm(MatSet ms, int S, i
   const long ld = ms.ld;
   if (t == ntk * SUB) {   // tile (ia, ia) of column ia, panels [0, k)
     double* C = M + ia * MK_NB + (long)ia * MK_NB * ld;
+    if (syrk) {
+      AccSyrk a;
+      acc_load_syrk(a, C, ld);
+      gemm_syrk_128(M + ia * MK_NB, ld, k * MK_NB, a, lds);
+      store_tile_syrk(C, ld, a);
+      return;
+    }
     Acc acc;
     acc_load(acc, C, ld);
     gemm_tile<128, 128, true, true, true>(M + ia * MK_NB, ld, M + ia * MK_NB, ld, k * MK_NB, k * MK_NB, acc, lds);
@@ -467,8 +494,8 @@ __global__ __launch_bounds__(256, 2) void k_chol_update_trsm(MatSet ms, int S, i
     __syncthreads();
   }
 }
-template __global__ void k_chol_update_trsm<128>(MatSet, int, int, int, int, int, int, int, int, const int*, const int*);
-template __global__ void k_chol_update_trsm<64>(MatSet, int, int, int, int, int, int, int, int, const int*, const int*);
+template __global__ void k_chol_update_trsm<128>(MatSet, int, int, int, int, int, int, int, int, const int*, const int*, int);
+template __global__ void k_chol_update_trsm<64>(MatSet, int, int, int, int, int, int, int, int, const int*, const int*, int);
 
 // ---------------------------------------------------------------- diagonal tile: factor + invert in LDS
 // 128x128 tile T (column-major, stride TLD) in LDS, 256 threads, blocked by 16 (see
@@ -916,10 +943,11 @@ __device__ void factor_invert_tile(double* T, double* dg, double* xd, double* Sb
 // cj0 < cj1 (the fused factorisation, launch_cholesky): the tile first takes its update by panels
 // [cj0, cj1) -- k_chol_update's MFMA sequence from the tile in memory, the accumulator written
 // straight into the LDS image instead of back to HBM (the launch it replaces would have stored
-// exactly these values) -- then factors.
+// exactly these values) -- then factors.  syrk: the update in the balanced lower-block form
+// (gemm_syrk_128: 9 MFMAs per wave and k-step instead of 16, on the serial chain); 0: the full square.
 __global__ __launch_bounds__(256) void k_chol_diag(MatSet ms, const int* __restrict__ n_s, int h0, int hc, int k,
                                                    double* ld_part, double* quad_c, int* info, const int* slist,
-                                                   const int* scount, int cj0, int cj1) {
+                                                   const int* scount, int cj0, int cj1, int syrk) {
   extern __shared__ __attribute__((aligned(16))) double sm[];
   double* T = sm;                      // [128*128]
   double* dg = T + MK_NB * TLD;        // [128]
@@ -936,7 +964,12 @@ __global__ __launch_bounds__(256) void k_chol_diag(MatSet ms, const int* __restr
   const int base = k * MK_NB;
   const int ns = n_s[s];
   double* Mt = M + base + (long)base * ld;
-  if (cj1 > cj0) {
+  if (cj1 > cj0 && syrk) {
+    AccSyrk a;
+    acc_load_syrk(a, Mt, ld);
+    gemm_syrk_128(M + base + (long)cj0 * MK_NB * ld, ld, (cj1 - cj0) * MK_NB, a, sm);   // stages in T's space; ends with a barrier
+    store_tile_syrk_lds(T, TLD, a);
+  } else if (cj1 > cj0) {
     Acc acc;
     acc_load(acc, Mt, ld);
     const long jo = (long)cj0 * MK_NB * ld;

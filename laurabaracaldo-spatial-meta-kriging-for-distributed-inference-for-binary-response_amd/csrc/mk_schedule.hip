@@ -130,6 +130,17 @@ void mk::launch_candidates(const Model& md, const MatSet& ms, hipStream_t st, in
 // One launch per step covers outcomes h0 .. h0+hc-1 of every subset (hc = q in the sampler).
 // Launch pieces of the blocked Cholesky for panel k, tiles [ia, ib), on stream st.
 
+// MK_DIAG_SYRK (default 1, read once per process): the diagonal 128-tiles' updates -- the fused
+// launches' extra job, the correction folded into the diagonal launch, and the 128-tile instance of
+// k_chol_update -- run the balanced lower-block body (gemm_syrk_128, mk_gemm.hpp), and the fused
+// launches deal their (now shorter) extra jobs after the row jobs (xcd_map_tail); 0: the full-square
+// bodies in the former order.  An argument of the kernels, so one build serves both arms of an A/B;
+// same bits on every element that is read.
+static int diag_syrk() {
+  static const int on = env_int("MK_DIAG_SYRK", 1);
+  return on != 0;
+}
+
 static void chol_update(mk_session* s, Group& g, hipStream_t st, int h0, int hc, int k, int ia, int ib, int j0, int j1,
                         const int* slist, const int* scount, double flops) {
   const int E = g.S * hc, nti = ib - ia;
@@ -138,17 +149,17 @@ static void chol_update(mk_session* s, Group& g, hipStream_t st, int h0, int hc,
   if (tm == 32) {
     timed(s, st, KS_CHOL_UPDATE_SUB, flops, [&] {
       MK_LAUNCH(k_chol_update<32>, dim3(xcd_grid_h(E, nti * 16)), dim3(256), LDS_32, st, g.ms, g.S, h0, hc, k, ia,
-                         ib, j0, j1, slist, scount);
+                         ib, j0, j1, slist, scount, diag_syrk());
     });
   } else if (tm == 64) {
     timed(s, st, KS_CHOL_UPDATE_SUB, flops, [&] {
       MK_LAUNCH(k_chol_update<64>, dim3(xcd_grid_h(E, nti * 4)), dim3(256), LDS_64, st, g.ms, g.S, h0, hc, k, ia,
-                         ib, j0, j1, slist, scount);
+                         ib, j0, j1, slist, scount, diag_syrk());
     });
   } else {
     timed(s, st, KS_CHOL_UPDATE, flops, [&] {
       MK_LAUNCH(k_chol_update<128>, dim3(xcd_grid_h(E, nti)), dim3(256), LDS_128, st, g.ms, g.S, h0, hc, k, ia,
-                         ib, j0, j1, slist, scount);
+                         ib, j0, j1, slist, scount, diag_syrk());
     });
   }
 }
@@ -178,10 +189,10 @@ static void chol_update_trsm(mk_session* s, Group& g, hipStream_t st, int h0, in
   timed(s, st, tm == 128 ? KS_CHOL_UPDATE : KS_CHOL_UPDATE_SUB, flops, [&] {
     if (tm == 128)
       MK_LAUNCH(k_chol_update_trsm<128>, dim3(xcd_grid_h(E, nti + extra)), dim3(256), LDS_128, st, g.ms, g.S, h0, hc,
-                k, k + 1, nt, j0, extra, slist, scount);
+                k, k + 1, nt, j0, extra, slist, scount, diag_syrk());
     else
       MK_LAUNCH(k_chol_update_trsm<64>, dim3(xcd_grid_h(E, 2 * nti + extra)), dim3(256), LDS_128, st, g.ms, g.S, h0,
-                hc, k, k + 1, nt, j0, extra, slist, scount);
+                hc, k, k + 1, nt, j0, extra, slist, scount, diag_syrk());
   });
 }
 // cj0 < cj1: the diagonal tile's update by panels [cj0, cj1) first, in the same launch (fused form).
@@ -189,7 +200,7 @@ static void chol_diag(mk_session* s, Group& g, hipStream_t st, int h0, int hc, i
                       const int* scount, int cj0 = 0, int cj1 = 0, double flops = 0.0) {
   timed(s, st, KS_CHOL_DIAG, flops, [&] {
     MK_LAUNCH(k_chol_diag, dim3(g.S * hc), dim3(256), (size_t)MK_DIAG_LDS_BYTES, st, g.ms, g.md.n_s, h0, hc, k,
-                       g.md.ld_part, g.md.quad_c, g.md.info, slist, scount, cj0, cj1);
+                       g.md.ld_part, g.md.quad_c, g.md.info, slist, scount, cj0, cj1, diag_syrk());
   });
 }
 

@@ -158,6 +158,25 @@ __device__ inline bool xcd_map(int S, int T, int* s, int* t) {
   *t = w % T;
   return true;
 }
+// The same map with every entry's last item (t = T - 1, T >= 2) dealt after all the others: XCD x
+// takes its chunk of the S (T - 1) leading items first, then its chunk of the S last items.  Fits
+// the same grid: ceil(S (T-1) / 8) + ceil(S / 8) <= ceil(S / 8) T.
+__device__ inline bool xcd_map_tail(int S, int T, int* s, int* t) {
+  const int x = blockIdx.x & 7, j = blockIdx.x >> 3;
+  const int Wr = S * (T - 1), Cr = (Wr + 7) >> 3, Cs = (S + 7) >> 3;
+  if (j < Cr) {
+    const int w = x * Cr + j;
+    if (w >= Wr) return false;
+    *s = w / (T - 1);
+    *t = w % (T - 1);
+    return true;
+  }
+  const int e = x * Cs + (j - Cr);
+  if (j - Cr >= Cs || e >= S) return false;
+  *s = e;
+  *t = T - 1;
+  return true;
+}
 __host__ inline int xcd_grid(int S, int T) { return 8 * ((S + 7) / 8) * T; }
 
 
