@@ -181,7 +181,8 @@ int mk_session_tile_grids_wp(mk_session* s, int32_t t0, double* out_w, double* o
  * count, no timing; 12 tiles of a tiled session kriged by phi interpolation -- launches = tiles, flops
  * = exact kriging-variance evaluations, total_ms = the largest per-tile check difference (not a time);
  * 13 tiles whose check failed and were replayed exactly -- launches, total_ms = the largest failing
- * difference).  Flops are algorithmic, not executed: GEMM tiles 2 m n k, the diagonal tile's
+ * difference; 14 the chain-diagnostic launches k_chain_diag / k_chain_diag_prob -- launches and ms,
+ * timed whether or not profiling is on; 0 launches unless diagnostics were asked for).  Flops are algorithmic, not executed: GEMM tiles 2 m n k, the diagonal tile's
  * update as a SYRK, solves and inverse products over their triangles.  mk_session_profile(s, enable)
  * before mk_session_run: enable 0 = off, 1 = every kind, otherwise a mask with bit (1 + kind) per kind
  * bracketed (e.g. 2 << 0 = the panel update only; fewer events, less overhead). */
@@ -236,6 +237,53 @@ typedef struct mk_combined {
 typedef int (*mk_progress_fn)(void* user, int32_t iterations, int32_t n_samples);
 int mk_meta_fit(const mk_problem* prob, const mk_config* cfg, const int32_t* devices, int32_t n_devices,
                 mk_progress_fn progress, void* user, mk_outputs* out, mk_combined* comb);
+
+/* ---- chain diagnostics: the numerical counterpart of the trace plots (MK.R:147-149) ----
+ * Each chain is one column in time order, x_0 .. x_{n-1} (the kept states).  Per chain, on device:
+ *   m = (sum x_i)/n, d_i = x_i - m, c_t = (1/n) sum_{i=0}^{n-1-t} d_i d_{i+t}  (biased autocovariance)
+ *   Gamma_k = (c_2k + c_2k+1)/c_0 while 2k+1 <= n-1; Geyer's initial monotone sequence: stop at the
+ *   first Gamma_k <= 0 (not added), else Gamma_k <- min(Gamma_k, Gamma_k-1); tau = -1 + 2 sum Gamma_k,
+ *   tau <- max(tau, 1/log10(n))
+ *   ess = n/tau;  mcse = sqrt(c_0 n/(n-1) / ess)  (Monte Carlo s.e. of the column mean)
+ *   split R-hat: h = floor(n/2), a = x[0:h], b = x[n-h:n] (an odd n drops the middle state),
+ *   W = (var a + var b)/2 (h-1 denominators), B = h (mean a - mean b)^2 / 2,
+ *   rhat = sqrt(((h-1)/h W + B/h) / W).
+ * A column that never moved (c_0 = 0) gives (0, 0, +inf); W = 0 with c_0 > 0 gives rhat = +inf; any
+ * non-finite value gives three NaN.  4 <= n <= 16384 (the quantile summaries' limit), else MK_E_ARG.
+ * "Worst over subsets" is per column: min ess, max mcse, max rhat; a NaN in any subset makes that
+ * entry NaN.  The thresholds a reader applies to these numbers are the reader's own. */
+#define MK_N_DIAG 3   /* rows: ess, mcse, rhat */
+typedef struct mk_diagnostics {        /* caller-allocated, any pointer may be NULL */
+  double* parameters;        /* [n_subsets] x (3 x P)         column-major */
+  double* w_predict;         /* [n_subsets] x (3 x q*n_test)                */
+  double* p_predict;         /* the same of p = linkinv(x'beta + w); needs x_test */
+  double* parameters_worst;  /* 3 x P: worst over this call's subsets       */
+  double* w_predict_worst;   /* 3 x q*n_test                                */
+  double* p_predict_worst;   /* 3 x q*n_test                                */
+} mk_diagnostics;
+/* After all iterations.  parameters: rows burn_in .. n.samples of the recorded samples, or the kept
+ * window when mk_session_set_kept_window set one (sessions made for spPredict run with burn_in = 1,
+ * so there the window is the only meaningful range).  w_predict / p_predict: a fused session's
+ * kriging draws.  A tiled session's draws exist one tile at a time: asking for them here is MK_E_ARG;
+ * attach a sink (mk_session_set_diagnostics) and the tile replays fill it. */
+int mk_session_diagnostics(mk_session* s, mk_diagnostics* out);
+/* Tiled sessions: while a sink is attached (the struct is copied; NULL detaches), every tile replay
+ * -- mk_session_outputs, mk_session_tile_grids, mk_session_tile_grids_wp -- also diagnoses that
+ * tile's draws before it returns, from the same replay: columns [t0*q, t0*q + q*Tc) of the sink's
+ * w_predict / p_predict arrays (sized for all q*n_test columns) and of their worst rows.  The sink's
+ * parameters fields are not written (mk_session_diagnostics gives them).  p fields without x_test:
+ * MK_E_ARG.  mk_session_set_test_sites detaches the sink (its arrays were sized for the old sites). */
+int mk_session_set_diagnostics(mk_session* s, const mk_diagnostics* sink);
+/* mk_meta_fit with the diagnostics of all K subsets (mk_meta_fit is this call with diag = NULL): the
+ * per-subset arrays in global subset order, the worst rows over all K (each device block reduces
+ * its own on device, the calling thread folds the blocks).  Tiled kriging diagnoses each tile from
+ * the replay that makes its grids. */
+int mk_meta_fit_diag(const mk_problem* prob, const mk_config* cfg, const int32_t* devices, int32_t n_devices,
+                     mk_progress_fn progress, void* user, mk_outputs* out, mk_combined* comb, mk_diagnostics* diag);
+/* The diagnostic kernel on caller-given chains: x is n_rows x n_cols column-major, one chain per
+ * column (a coda mcmc matrix such as p.beta.theta.samples; t(p.w.samples) for the latent draws);
+ * out is 3 x n_cols column-major. */
+int mk_chain_diagnostics(const double* x, int32_t n_rows, int64_t n_cols, double* out, int32_t device);
 
 /* ---- combine (MK.R:123-133): out = (grid_1 + ... + grid_K) / K, sequential order ---- */
 int mk_combine(const double* grids, int32_t K, int64_t grid_len, double* out, int32_t device);

@@ -24,6 +24,7 @@ MK_COV_MATERN = 1
 MK_LINK_LOGIT = 0
 MK_LINK_PROBIT = 1
 N_LEVELS = 200
+N_DIAG = 3             # MK_N_DIAG: rows ess, mcse, rhat
 
 _dp = ctypes.POINTER(ctypes.c_double)
 _ip = ctypes.POINTER(ctypes.c_int32)
@@ -71,12 +72,23 @@ class Combined(ctypes.Structure):
                 ("tol", ctypes.c_double), ("exchange", ctypes.c_int32), ("comm_ranks", ctypes.c_int32), ("result3", _dp)]
 
 
+class Diagnostics(ctypes.Structure):
+    _fields_ = [("parameters", _dp), ("w_predict", _dp), ("p_predict", _dp), ("parameters_worst", _dp),
+                ("w_predict_worst", _dp), ("p_predict_worst", _dp)]
+
+
 # int (*mk_progress_fn)(void* user, int32_t iterations, int32_t n_samples)
 PROGRESS_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32)
 
 EXPORTS = {
     "mk_meta_fit": (ctypes.c_int, [ctypes.POINTER(Problem), ctypes.POINTER(Config), _ip, ctypes.c_int32,
                                    PROGRESS_FN, ctypes.c_void_p, ctypes.POINTER(Outputs), ctypes.POINTER(Combined)]),
+    "mk_meta_fit_diag": (ctypes.c_int, [ctypes.POINTER(Problem), ctypes.POINTER(Config), _ip, ctypes.c_int32,
+                                        PROGRESS_FN, ctypes.c_void_p, ctypes.POINTER(Outputs), ctypes.POINTER(Combined),
+                                        ctypes.POINTER(Diagnostics)]),
+    "mk_session_diagnostics": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(Diagnostics)]),
+    "mk_session_set_diagnostics": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(Diagnostics)]),
+    "mk_chain_diagnostics": (ctypes.c_int, [_dp, ctypes.c_int32, ctypes.c_int64, _dp, ctypes.c_int32]),
     "mk_session_create": (ctypes.c_int, [ctypes.POINTER(Problem), ctypes.POINTER(Config), ctypes.POINTER(ctypes.c_void_p)]),
     "mk_session_run": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32]),
     "mk_session_iteration": (ctypes.c_int32, [ctypes.c_void_p]),

@@ -109,6 +109,10 @@ __global__ void k_quantiles(const double* data, long subset_stride, long row_str
 __global__ void k_quantiles_prob(const double* data, long subset_stride, long row_stride, int n_rows, int n_cols,
                                  const double* probs, int n_probs, double* out, ProbSrc ps);
 __global__ void k_pred_prob(const double* w, long row_stride, int n_rows, int n_cols, double* out, ProbSrc ps);
+__global__ void k_chain_diag(const double* data, long subset_stride, long row_stride, int n_rows, int n_cols, double* out);
+__global__ void k_chain_diag_prob(const double* data, long subset_stride, long row_stride, int n_rows, int n_cols,
+                                  double* out, ProbSrc ps);
+__global__ void k_diag_worst(const double* d, int S, long C, double* out);
 __global__ void k_combine(const double* grids, int K, long G, double* out, int mean);
 __global__ void k_record_kept(Model md, int kidx);
 __global__ void k_kept_dirty(Model md, const double* th_prev, int* slist, int* scount, int* plist, int* pcount);

@@ -111,6 +111,8 @@ extern "C" int mk_session_set_test_sites(mk_session* s, int32_t n_test, const do
   if (n_test < 1 || !coords_test) return set_err(MK_E_ARG, "n_test must be >= 1 with coordinates");
   MK_ENTRY_DEVICE(s->device);
   HIPCHK(hipStreamSynchronize(s->stream));
+  s->diag_on = false;                      // a diagnostics sink was sized for the sites that go
+  s->diag_sink = mk_diagnostics{};
   int rc = set_test_covars(s, nullptr);   // the covariates belonged to the sites that go
   if (rc) return rc;
   return kriging_buffers(s, n_test, coords_test);
@@ -208,6 +210,11 @@ static int tile_outputs(mk_session* s, int t0, double* dq, double* dqp, mk_outpu
       HIPCHK(hipMemcpy2DAsync(o->w_pred_samples + (size_t)i * n_kept * C + (size_t)t0 * q, (size_t)C * 8,
                               md.w_pred + (size_t)i * n_kept * Ct, (size_t)Ct * 8, (size_t)Ct * 8, n_kept,
                               hipMemcpyDeviceToHost, st));
+  // an attached diagnostics sink: this tile's columns, while its draws exist (no second replay)
+  if (s->diag_on) {
+    const int rc = tile_diagnostics(s, t0, n_kept, Ct);
+    if (rc) return rc;
+  }
   HIPCHK(hipStreamSynchronize(st));
   return 0;
 }
@@ -553,6 +560,8 @@ static int predict_tile_cheb(mk_session* s, int t0, double* dq, mk_outputs* o, d
 // o->w_pred_samples / o->p_pred_samples, its draws to the host.  Returns after the stream is idle.
 int mk::predict_tile(mk_session* s, int t0, double* dq, mk_outputs* o, double* dqp) {
   if ((dqp || (o && o->p_pred_samples)) && !s->d_xt) return set_err(MK_E_ARG, "predictive probabilities need x_test");
+  if (s->diag_on && (s->diag_sink.p_predict || s->diag_sink.p_predict_worst) && !s->d_xt)
+    return set_err(MK_E_ARG, "the diagnostics sink asks for p_predict: that needs x_test");
   const int rc_cheb = predict_tile_cheb(s, t0, dq, o, dqp);
   if (rc_cheb != MK_CHEB_EXACT) return rc_cheb;
   Model& md = s->md;

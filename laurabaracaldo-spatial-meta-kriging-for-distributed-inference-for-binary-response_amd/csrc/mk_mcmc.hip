@@ -1659,6 +1659,174 @@ __global__ __launch_bounds__(256) void k_pred_prob(const double* __restrict__ w,
                      ps.link);
 }
 
+// ---------------------------------------------------------------- 8b. chain diagnostics
+// The numerical counterpart of the reference's trace plots (MK.R:147-149): per (subset, column) the
+// effective sample size by Geyer's initial monotone sequence, the Monte Carlo s.e. of the column mean
+// and the split R-hat of the n_rows kept values, read as k_quantiles reads them but kept in time
+// order (the sort of section 8 destroys it, hence a kernel of its own).  One 256-thread workgroup
+// per chain, the chain in dynamic LDS (n_rows doubles, at most MK_QUANT_MAX = 128 KB):
+//   m = sum x / n, d = x - m (centred in place); c_t = (1/n) sum_i d_i d_{i+t};
+//   Gamma_k = (c_2k + c_2k+1) / c_0 while 2k + 1 <= n - 1, stopped at the first Gamma_k <= 0 (not
+//   added), else Gamma_k = min(Gamma_k, Gamma_k-1); tau = max(-1 + 2 sum Gamma_k, 1 / log10 n);
+//   ess = n / tau; mcse = sqrt(c_0 n / (n - 1) / ess);
+//   h = n / 2, halves a = x[0:h], b = x[n-h:n]; W = (var a + var b) / 2 (h - 1 denominators),
+//   B = h (mean a - mean b)^2 / 2; rhat = sqrt(((h - 1) / h W + B / h) / W).
+// A column that never moved (or c_0 = 0) gives (0, 0, +inf); W = 0 gives rhat = +inf; a non-finite
+// value gives three NaN (decided before the lag loop, which therefore always ends).
+// Every sum runs in an order that depends on n only: thread t adds its elements t, t + 256, ... in
+// turn, then the wave's butterfly, then the four waves in wave order -- so the numbers do not depend
+// on the grid, the tile or the path that made the draws.  The lag products are taken MK_DIAG_LAGS
+// lags at a time (one accumulator per lag and thread, explicit fma; consecutive lanes read
+// consecutive doubles of LDS) and the Gamma sequence is evaluated after each block by every thread
+// alike, so the exit at the first Gamma_k <= 0 is uniform.  The closing formulas are plain
+// products and quotients in the order written above (no FMA contraction, as in quant_sort_readout).
+constexpr int MK_DIAG_LAGS = 16;
+
+// a[k] <- the workgroup's sum of a[k], in every thread; red: [4][MK_DIAG_LAGS] of LDS.  One barrier:
+// callers alternate between two such buffers, so a wave can reach the next write of a buffer only
+// after every wave has passed the barrier that follows its last read.
+template <int K>
+__device__ inline void diag_block_sum(double (&a)[K], double (*red)[MK_DIAG_LAGS]) {
+#pragma unroll
+  for (int k = 0; k < K; ++k)
+    for (int off = 32; off > 0; off >>= 1) a[k] = a[k] + __shfl_xor(a[k], off);
+  if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+    for (int k = 0; k < K; ++k) red[threadIdx.x >> 6][k] = a[k];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < K; ++k) a[k] = ((red[0][k] + red[1][k]) + red[2][k]) + red[3][k];
+}
+
+template <bool PROB>
+__device__ inline void chain_diag(const double* __restrict__ data, long subset_stride, long row_stride, int n,
+                                  int n_cols, double* __restrict__ out /* [S][n_cols][3] */, const ProbSrc& ps) {
+  extern __shared__ double v[];
+  __shared__ double red[2][4][MK_DIAG_LAGS];
+  const int s = blockIdx.x / n_cols, c = blockIdx.x % n_cols, tid = threadIdx.x;
+  const double* src = data + (long)s * subset_stride + c;
+  const double* beta = PROB ? ps.samples + (long)s * ps.subset_stride : nullptr;
+  const double* xrow = PROB ? ps.x + ps.x_off + c : nullptr;
+  auto value = [&](int r) {
+    const double w = src[(long)r * row_stride];
+    return PROB ? pred_prob(xrow, ps.ldx, beta + (long)r * ps.row_stride, ps.p, w, ps.link) : w;
+  };
+  double* o = out + ((long)s * n_cols + c) * 3;
+  const double dn = (double)n;
+  int par = 0;
+  // the chain into LDS in time order; its sum, and whether any value differs from the first
+  const double x0 = value(0);
+  double f[2] = {0.0, 0.0};
+  for (int r = tid; r < n; r += 256) {
+    const double x = value(r);
+    v[r] = x;
+    f[0] = f[0] + x;
+    if (x != x0) f[1] = 1.0;
+  }
+  diag_block_sum(f, red[par]);
+  par ^= 1;
+  if (!isfinite(f[0])) {   // a NaN or an infinity in the column (uniform: every thread holds the same sum)
+    if (tid == 0) o[0] = o[1] = o[2] = NAN;
+    return;
+  }
+  if (f[1] == 0.0) {       // the column never moved
+    if (tid == 0) { o[0] = 0.0; o[1] = 0.0; o[2] = INFINITY; }
+    return;
+  }
+  const double m = f[0] / dn;
+  const int h = n / 2;
+  // centre in place; the halves' sums of d (the middle state of an odd n belongs to neither)
+  double g[2] = {0.0, 0.0};
+  for (int r = tid; r < n; r += 256) {
+    const double d = v[r] - m;
+    v[r] = d;
+    if (r < h) g[0] = g[0] + d;
+    if (r >= n - h) g[1] = g[1] + d;
+  }
+  diag_block_sum(g, red[par]);
+  par ^= 1;
+  const double da = g[0] / h, db = g[1] / h;   // mean a - m, mean b - m
+  // the fixed sums in one pass: c_0 and both halves' sums of squares about their own means
+  double q3[3] = {0.0, 0.0, 0.0};
+  for (int r = tid; r < n; r += 256) {
+    const double d = v[r];
+    q3[0] = fma(d, d, q3[0]);
+    if (r < h) q3[1] = fma(d - da, d - da, q3[1]);
+    if (r >= n - h) q3[2] = fma(d - db, d - db, q3[2]);
+  }
+  diag_block_sum(q3, red[par]);
+  par ^= 1;
+  const double c0 = q3[0] / dn;
+  if (!(c0 > 0.0)) {
+    if (tid == 0) { o[0] = 0.0; o[1] = 0.0; o[2] = INFINITY; }
+    return;
+  }
+  // Geyer's initial monotone sequence over blocks of MK_DIAG_LAGS lags (a pair (2k, 2k + 1) never
+  // straddles two blocks)
+  double tau = -1.0, prev = INFINITY;
+  bool stop = false;
+  for (int t0 = 0; t0 <= n - 1 && !stop; t0 += MK_DIAG_LAGS) {
+    double a[MK_DIAG_LAGS];
+#pragma unroll
+    for (int l = 0; l < MK_DIAG_LAGS; ++l) a[l] = 0.0;
+    for (int i = tid; i + t0 < n; i += 256) {
+      const double di = v[i];
+#pragma unroll
+      for (int l = 0; l < MK_DIAG_LAGS; ++l)
+        if (i + t0 + l < n) a[l] = fma(di, v[i + t0 + l], a[l]);
+    }
+    diag_block_sum(a, red[par]);
+    par ^= 1;
+#pragma unroll
+    for (int l = 0; l < MK_DIAG_LAGS; l += 2) {
+      if (stop) continue;
+      if (t0 + l + 1 > n - 1) { stop = true; continue; }
+      double gk = (a[l] / dn + a[l + 1] / dn) / c0;
+      if (!(gk > 0.0)) { stop = true; continue; }
+      gk = fmin(gk, prev);
+      prev = gk;
+      tau = tau + 2.0 * gk;
+    }
+  }
+  if (tid != 0) return;
+  tau = fmax(tau, 1.0 / log10(dn));
+  const double ess = dn / tau;
+  o[0] = ess;
+  o[1] = sqrt(c0 * dn / (dn - 1.0) / ess);
+  const double W = 0.5 * (q3[1] / (h - 1) + q3[2] / (h - 1));
+  const double dm = da - db;
+  const double B = h * 0.5 * (dm * dm);
+  o[2] = W > 0.0 ? sqrt(((double)(h - 1) / h * W + B / h) / W) : INFINITY;
+}
+
+__global__ __launch_bounds__(256) void k_chain_diag(const double* __restrict__ data, long subset_stride, long row_stride,
+                                                    int n_rows, int n_cols, double* __restrict__ out) {
+  chain_diag<false>(data, subset_stride, row_stride, n_rows, n_cols, out, ProbSrc{});
+}
+
+// The same of p = pred_prob(draw), transformed as LDS is filled (k_quantiles_prob's arguments).
+__global__ __launch_bounds__(256) void k_chain_diag_prob(const double* __restrict__ data, long subset_stride,
+                                                         long row_stride, int n_rows, int n_cols,
+                                                         double* __restrict__ out, ProbSrc ps) {
+  chain_diag<true>(data, subset_stride, row_stride, n_rows, n_cols, out, ps);
+}
+
+// Worst over subsets, per column: min ess, max mcse, max rhat of d [S][C][3] into out [C][3]; a NaN
+// in any subset makes that entry NaN.
+__global__ __launch_bounds__(256) void k_diag_worst(const double* __restrict__ d, int S, long C, double* __restrict__ out) {
+  const long e = (long)blockIdx.x * 256 + threadIdx.x;
+  if (e >= C * 3) return;
+  const bool is_min = e % 3 == 0;
+  double w = d[e];
+  for (int s = 1; s < S; ++s) {
+    const double x = d[(long)s * C * 3 + e];
+    if (w != w) break;
+    w = (x != x) ? x : (is_min ? fmin(w, x) : fmax(w, x));
+  }
+  out[e] = w;
+}
+
 // ---------------------------------------------------------------- 9. combine (MK.R:123-133)
 // out = (((g_0 + g_1) + g_2) + ...) / K : the reference's sequential order (mean = 0: the sum only,
 // one shard's term of the combine).

@@ -376,10 +376,27 @@ int exchange_combine(Node& nd, long C, const mk_combined* comb, double* h_comb, 
   });
 }
 
+// Worst rows of one block folded into the node's (both [n][3]: min ess, max mcse, max rhat; a NaN
+// on either side stays).  min and max are exact, so the order of the blocks does not matter.
+void fold_worst(double* into, const double* blk, long n, bool first) {
+  for (long e = 0; e < n * MK_N_DIAG; ++e) {
+    const double a = into[e], b = blk[e];
+    if (first) into[e] = b;
+    else if (a != a || b != b) into[e] = a != a ? a : b;
+    else into[e] = (e % MK_N_DIAG == 0) ? std::min(a, b) : std::max(a, b);
+  }
+}
+
 }  // namespace
 
 extern "C" int mk_meta_fit(const mk_problem* pr, const mk_config* c, const int32_t* devices, int32_t G,
                            mk_progress_fn progress, void* user, mk_outputs* out, mk_combined* comb) {
+  return mk_meta_fit_diag(pr, c, devices, G, progress, user, out, comb, nullptr);
+}
+
+extern "C" int mk_meta_fit_diag(const mk_problem* pr, const mk_config* c, const int32_t* devices, int32_t G,
+                                mk_progress_fn progress, void* user, mk_outputs* out, mk_combined* comb,
+                                mk_diagnostics* diag) {
   if (!pr || !c) return fail(MK_E_ARG, "null problem/config");
   if (!devices || G < 1) return fail(MK_E_ARG, "n_devices must be >= 1 with a device list");
   const int K = pr->n_subsets;
@@ -397,6 +414,10 @@ extern "C" int mk_meta_fit(const mk_problem* pr, const mk_config* c, const int32
     if (pr->n_part[i] < 1) return fail(MK_E_ARG, "every subset needs >= 1 site");
   const bool want_p = (out && (out->p_predict || out->p_pred_samples || out->p_predict_sum)) || (comb && comb->result3);
   if (want_p && !pr->x_test) return fail(MK_E_ARG, "p_predict / p_pred_samples / p_predict_sum / result3 need x_test");
+  const bool dg_par = diag && (diag->parameters || diag->parameters_worst);
+  const bool dg_w = diag && (diag->w_predict || diag->w_predict_worst);
+  const bool dg_p = diag && (diag->p_predict || diag->p_predict_worst);
+  if (dg_p && !pr->x_test) return fail(MK_E_ARG, "p_predict diagnostics need x_test");
   const int q = pr->q, p = pr->p, n_samples = c->n_batch * c->batch_length;
   if (c->n_batch < 1 || c->batch_length < 1) return fail(MK_E_ARG, "n.batch and batch.length must be >= 1");
 
@@ -512,6 +533,43 @@ extern "C" int mk_meta_fit(const mk_problem* pr, const mk_config* c, const int32
   });
   if (rc) return rc;
 
+  // ---- chain diagnostics (optional): every block writes its subsets' slice of the per-subset arrays
+  // and reduces its own worst rows on device into bw; the calling thread folds the blocks.  A tiled
+  // block gets a sink with those pointers, so the one replay per tile below serves its grids and its
+  // diagnostics together.
+  std::vector<std::vector<double>> bw(G);   // per block: worst rows of the parameters [P][3] | w [C][3] | p [C][3]
+  auto shard_diag = [&](int r) {
+    const Block& x = *nd.b[r];
+    mk_diagnostics d{};
+    double* w0 = bw[r].data();
+    if (diag->parameters) d.parameters = diag->parameters + (size_t)x.lo * P * MK_N_DIAG;
+    if (diag->w_predict) d.w_predict = diag->w_predict + (size_t)x.lo * C * MK_N_DIAG;
+    if (diag->p_predict) d.p_predict = diag->p_predict + (size_t)x.lo * C * MK_N_DIAG;
+    if (diag->parameters_worst) d.parameters_worst = w0;
+    if (diag->w_predict_worst) d.w_predict_worst = w0 + (size_t)P * MK_N_DIAG;
+    if (diag->p_predict_worst) d.p_predict_worst = w0 + (size_t)(P + C) * MK_N_DIAG;
+    return d;
+  };
+  if (dg_par || ((dg_w || dg_p) && n_test > 0)) {
+    for (int r = 0; r < G; ++r) bw[r].assign((size_t)(P + 2 * C) * MK_N_DIAG, 0.0);
+    rc = nd.pool->run([&](int r) -> int {
+      Block& x = *nd.b[r];
+      if (!x.ses) return 0;
+      mk_diagnostics d = shard_diag(r);
+      if (tiled || n_test < 1) {   // the kriging draws of a tiled block: its sink, filled tile by tile
+        mk_diagnostics sink = d;
+        sink.parameters = sink.parameters_worst = nullptr;
+        d.w_predict = d.p_predict = d.w_predict_worst = d.p_predict_worst = nullptr;
+        if (tiled && n_test > 0) {
+          const int e = mk_session_set_diagnostics(x.ses, &sink);
+          if (e) return e;
+        }
+      }
+      return mk_session_diagnostics(x.ses, &d);
+    });
+    if (rc) return rc;
+  }
+
   // ---- the grids.  A whole grid kind ([S_r][Ck][200] per block, in x.grids): each block's grids to its subsets'
   // slice of h_each, then the exchange + combine.
   auto whole_grids = [&](GridKind kind, long Ck, double* h_each, double* h_comb, double* h_sum) -> int {
@@ -539,7 +597,7 @@ extern "C" int mk_meta_fit(const mk_problem* pr, const mk_config* c, const int32
     const PredKind pk{GRID_P, out ? out->p_predict : nullptr, out ? out->p_predict_sum : nullptr,
                       comb ? comb->result3 : nullptr, &Block::grids_p};
     const bool draws = out && (out->w_pred_samples || out->p_pred_samples);
-    const bool replay = tiled && (w.asked() || pk.asked() || draws);   // one replay per tile serves them all
+    const bool replay = tiled && (w.asked() || pk.asked() || draws || dg_w || dg_p);   // one replay per tile serves them all
     if (!tiled) {
       for (const PredKind* k : {&pk, &w})   // p before w
         if (k->asked() && (rc = whole_grids(k->kind, C, k->h_each, k->h_comb, k->h_sum))) return rc;
@@ -576,6 +634,17 @@ extern "C" int mk_meta_fit(const mk_problem* pr, const mk_config* c, const int32
         for (const PredKind* k : {&w, &pk})   // w before p
           if ((rc = exchange_combine(nd, Ct, comb, at_tile(k->h_comb), at_tile(k->h_sum), k->tile))) return rc;
       }
+    }
+  }
+  if (diag) {   // the worst rows over all K: the blocks' own, folded here
+    bool first = true;
+    for (int r = 0; r < G; ++r) {
+      if (!nd.b[r]->ses || bw[r].empty()) continue;
+      const double* w0 = bw[r].data();
+      if (diag->parameters_worst) fold_worst(diag->parameters_worst, w0, P, first);
+      if (diag->w_predict_worst && n_test > 0) fold_worst(diag->w_predict_worst, w0 + (size_t)P * MK_N_DIAG, C, first);
+      if (diag->p_predict_worst && n_test > 0) fold_worst(diag->p_predict_worst, w0 + (size_t)(P + C) * MK_N_DIAG, C, first);
+      first = false;
     }
   }
   return 0;

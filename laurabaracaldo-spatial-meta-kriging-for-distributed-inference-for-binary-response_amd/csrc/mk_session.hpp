@@ -6,6 +6,7 @@
 //   mk_krig.hip      the kriging buffers, the phi tables and the tiled replay
 //   mk_summary.hip   stateless entry points (combine, Weiszfeld, posterior summary, glm): no session
 //   mk_parity.hip    parity-test entry points
+//   mk_diag.hip      chain diagnostics: the launcher, the session entry points, the tile sink
 //
 // mk_internal.hpp stays the interface towards mk_multi.hip and mk_watch.hip.
 #pragma once
@@ -46,7 +47,7 @@ static inline int env_int(const char* name, int dflt) {
   return (v && *v) ? std::atoi(v) : dflt;
 }
 
-constexpr int NKSTAT = 14;
+constexpr int NKSTAT = 15;
 // KS_CHOL_UPDATE: the 128-tile panel-update launches (k_chol_update<128>); KS_CHOL_UPDATE_SUB:
 // the 64- / 32-sub-tile ones (small grids).  Together: the roofline kernel k_chol_update.
 // KS_UPDATE_BUSY: both, with the time of launches that overlap (the split schedule's bulk and
@@ -55,11 +56,13 @@ constexpr int NKSTAT = 14;
 // bound: only the pairs whose factor changed are in the list -- bench_kriging counts exactly).
 // KS_COV: the candidates' covariance assembly (k_cov_candidate, with k_matern_table for Matern).
 enum { KS_CHOL_UPDATE = 0, KS_CHOL_DIAG, KS_CHOL_TRSM, KS_SWEEP, KS_LAUUM, KS_ITER, KS_INV, KS_CHOL_UPDATE_SUB,
-       KS_UPDATE_BUSY, KS_PRED_VAR, KS_COV, KS_SWEEP_FALLBACK, KS_KRIG_CHEB, KS_KRIG_FALLBACK };
+       KS_UPDATE_BUSY, KS_PRED_VAR, KS_COV, KS_SWEEP_FALLBACK, KS_KRIG_CHEB, KS_KRIG_FALLBACK, KS_DIAG };
 // KS_KRIG_CHEB: tiles kriged by phi interpolation (predict_tile_cheb): launches = tiles, flops = exact
 // s evaluations ((subset, node or check point) pairs), total_ms = the largest check difference seen
 // (not a time).  KS_KRIG_FALLBACK: tiles whose check failed and were replayed exactly (launches), and
 // total_ms the largest failing difference.
+// KS_DIAG: the chain-diagnostic launches (k_chain_diag, k_chain_diag_prob), bracketed by events whether
+// or not the profiler is on (a handful per call, each followed by a wait anyway).
 // KS_SWEEP_FALLBACK: launches = (subset, iteration) sweeps k_sweep_mg refused admission and its
 // k_sweep fallback ran (counted on the device, read at the end of every mk_session_run; no timing).
 
@@ -243,6 +246,8 @@ struct mk_session {
   mk::ChebWindow cg;
   mk::SweepPlan sweep;
   mk::Profiler prof;
+  mk_diagnostics diag_sink{};           // mk_session_set_diagnostics: filled by every tile replay while diag_on
+  bool diag_on = false;
   hipError_t launch_err = hipSuccess;   // first failed kernel launch of a run
   const char* poisoned = nullptr;       // set when a run left the chain in a state that is not the sampler's
   std::vector<int> n_part;
@@ -344,5 +349,18 @@ ProbSrc prob_src(const mk_session* s, int t0);
 // scratch (n_rows * n_cols doubles), then rows ld_dst apart at dst (stream-ordered, not waited for)
 int pred_prob_to_host(mk_session* s, int subset, int t0, int n_rows, int n_cols, double* scratch, double* dst,
                       size_t ld_dst);
+
+// ---- mk_diag.hip
+// k_chain_diag (ps == NULL) or k_chain_diag_prob of grid chains, n_rows values each (4 .. MK_QUANT_MAX,
+// else MK_E_ARG), addressed as launch_quantiles addresses them; out [grid][3] in HBM.  Not waited for.
+int launch_chain_diag(unsigned grid, hipStream_t st, const double* data, long subset_stride, long row_stride,
+                      int n_rows, int n_cols, double* out, const ProbSrc* ps);
+// The diagnostics of the session's S x Ct chains in a draw or sample buffer to the host: every subset's
+// [Ct][3] into columns [col0, col0 + Ct) of its [C][3] array at h_each, the worst rows into the same
+// columns of h_worst ([C][3]); either may be NULL.  Timed as KS_DIAG; returns after the stream is idle.
+int diag_to_host(mk_session* s, const double* data, long subset_stride, long row_stride, int n_rows, long Ct,
+                 const ProbSrc* ps, long col0, long C, double* h_each, double* h_worst);
+// The attached sink's share of tile [t0, ..): the draws are in md.w_pred ([S][n_kept][Ct]).
+int tile_diagnostics(mk_session* s, int t0, int n_kept, int Ct);
 
 }  // namespace mk

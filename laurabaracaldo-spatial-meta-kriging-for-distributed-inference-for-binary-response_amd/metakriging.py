@@ -89,10 +89,12 @@ def r_sample_replace(n, size, seed):
 
 
 def meta_fit(y, x, weight, coords, q, index_part, coords_test=None, cfg=None, subset_base=0, device=0,
-             cov_model="exponential", n_batch=100, batch_length=50, seed=20250114, x_test=None):
+             cov_model="exponential", n_batch=100, batch_length=50, seed=20250114, x_test=None, diagnostics=False):
     """All subsets of one shard on one GPU; returns the list `obj` of MK.R:108 for those subsets:
     [{'parameters': 200 x P, 'w.predict': 200 x (q n_test)}, ...]; with x_test (MK.R:87's x.test) each
-    also holds 'p.predict' (200 x (q n_test)): the grid of p(y = 1) at the test sites."""
+    also holds 'p.predict' (200 x (q n_test)): the grid of p(y = 1) at the test sites.
+    diagnostics=True: each also holds 'parameters.diagnostics' (3 x P: ess, mcse, split R-hat of its kept
+    chain) and, with test sites, 'w.predict.diagnostics' / 'p.predict.diagnostics' (3 x (q n_test))."""
     p = np.asarray(x).shape[1]
     if cfg is None:
         beta0, bt = start_values(y, x, weight, q)
@@ -101,7 +103,7 @@ def meta_fit(y, x, weight, coords, q, index_part, coords_test=None, cfg=None, su
     subsets = [subset_data(y, x, weight, coords, q, idx) for idx in index_part]
     with Session(subsets, cfg, coords_test=coords_test, subset_base=subset_base, device=device, x_test=x_test) as ses:
         ses.run(cfg.n_samples)
-        out = ses.outputs()
+        out = ses.outputs(diagnostics=diagnostics)
     res = []
     for i in range(len(subsets)):
         d = {"parameters": out["parameters"][i]}
@@ -109,6 +111,9 @@ def meta_fit(y, x, weight, coords, q, index_part, coords_test=None, cfg=None, su
             d["w.predict"] = out["w_predict"][i]
         if "p_predict" in out:
             d["p.predict"] = out["p_predict"][i]
+        for kind in ("parameters", "w_predict", "p_predict"):
+            if kind + "_diag" in out:
+                d[kind.replace("_", ".") + ".diagnostics"] = out[kind + "_diag"][i]
         res.append(d)
     return res
 
@@ -152,6 +157,38 @@ def combine_predictive(obj, device=0, method="mean"):
     return combiner(method, device)([o["p.predict"] for o in obj])
 
 
+def convergence_report(diag, ess_min=100, rhat_max=1.05):
+    """Counts over the chain diagnostics Session.outputs / meta_fit_node return with diagnostics=True
+    (any dict holding '<kind>_diag' -- a list of 3 x C arrays, rows ess, mcse, rhat -- and / or
+    '<kind>_diag_worst', kind in parameters, w_predict, p_predict).  Per kind present: 'chains' counted
+    (every subset's columns, or the worst rows when only they are given), 'columns', 'ess_below'
+    (ess < ess_min), 'rhat_above' (rhat > rhat_max; a chain that never moved has rhat = inf),
+    'not_finite' (chains with a NaN), 'min_ess' / 'max_mcse' / 'max_rhat' over the finite entries and
+    the columns 'min_ess_column' / 'max_rhat_column' (0-based) where they occur.  The thresholds are
+    the caller's: common working values, not pass / fail rules of the library."""
+    rep = {}
+    for kind in ("parameters", "w_predict", "p_predict"):
+        per, worst = diag.get(kind + "_diag"), diag.get(kind + "_diag_worst")
+        if per is None and worst is None:
+            continue
+        a = np.stack([np.asarray(x, float) for x in per]) if per is not None else np.asarray(worst, float)[None]
+        if worst is None:       # min ess, max mcse, max rhat; a NaN in any subset stays
+            worst = np.where(np.isnan(a).any(axis=0), np.nan,
+                             np.stack([a[:, 0].min(axis=0), a[:, 1].max(axis=0), a[:, 2].max(axis=0)]))
+        worst = np.asarray(worst, float)
+        ess, rhat = a[:, 0], a[:, 2]
+        r = dict(chains=int(ess.size), columns=int(a.shape[2]), ess_below=int((ess < ess_min).sum()),
+                 rhat_above=int((rhat > rhat_max).sum()), not_finite=int(np.isnan(a).any(axis=1).sum()))
+        for name, row, pick in (("min_ess", 0, np.nanargmin), ("max_mcse", 1, np.nanargmax), ("max_rhat", 2, np.nanargmax)):
+            ok = not np.isnan(worst[row]).all()
+            col = int(pick(worst[row])) if ok else None
+            r[name] = float(worst[row][col]) if ok else None
+            if name != "max_mcse":
+                r[name + "_column"] = col
+        rep[kind] = r
+    return rep
+
+
 def posterior_summary(result, result2, x_test, q=None, samplesize=1000, seed=20250114, device=0, rng="philox",
                       index=None, link="logit"):
     """MK.R:136-165 on device: interpolate both combined grids to Xout (996 levels), one shared
@@ -165,7 +202,7 @@ def posterior_summary(result, result2, x_test, q=None, samplesize=1000, seed=202
 
 def reference_flow(d, K, q, cov_model="exponential", n_batch=100, batch_length=50, seed=20250114, devices=(0,),
                    method="mean", predict_tile=0, partition_method="R", samplesize=1000, progress=None,
-                   predictive=False):
+                   predictive=False, diagnostics=False):
     """The reference script end to end in one process over the GPUs in `devices` (mk_meta_fit: the
     subsets sharded over them in-library, the combine device to device):
 
@@ -179,6 +216,8 @@ def reference_flow(d, K, q, cov_model="exponential", n_batch=100, batch_length=5
     d: synthetic.generate output.  progress(iterations, n_samples) is called between amcmc batches
     (return True to stop).  predictive=True hands d["x_test"] to the fit as MK.R:87's x.test: every
     subset's grids of p(y = 1) at the test sites are made and combined too, summary["result3"].
+    diagnostics=True: the worst-over-subsets chain diagnostics come back as summary["diagnostics"]
+    (the '*_diag_worst' arrays of meta_fit_node; convergence_report reads them).
     Returns (phases, result, result2, summary, cfg) -- phases in seconds of
     wall clock: set-up (partition, glm, subset slicing), the chains (to the last batch boundary),
     quantiles + combine, post-processing, and the whole."""
@@ -203,7 +242,8 @@ def reference_flow(d, K, q, cov_model="exponential", n_batch=100, batch_length=5
         return bool(progress(it, n_samples)) if progress is not None else False
 
     fit = meta_fit_node(subs, cfg, coords_test=d["coords_test"], devices=devices, method=method, per_subset=False,
-                        progress=_progress, x_test=d["x_test"] if predictive else None)    # MK.R:100-133
+                        progress=_progress, x_test=d["x_test"] if predictive else None,
+                        diagnostics=diagnostics)                                            # MK.R:100-133
     t3 = time.perf_counter()
     t["chains_s"] = stamp.get("chains", t3) - t1
     t["quantiles_combine_s"] = t3 - stamp.get("chains", t3)
@@ -213,6 +253,8 @@ def reference_flow(d, K, q, cov_model="exponential", n_batch=100, batch_length=5
     t["post_s"] = time.perf_counter() - t2
     if "result3" in fit:
         summ["result3"] = fit["result3"]
+    if diagnostics:
+        summ["diagnostics"] = {k: v for k, v in fit.items() if k.endswith("_diag_worst")}
     t["end_to_end_s"] = time.perf_counter() - t0
     t["exchange"] = fit["exchange"]          # the combine's all-to-all: "rccl" (distinct GPUs) or "copy"
     t["comm_ranks"] = fit["comm_ranks"]      # ranks RCCL's communicators hold (copies: device blocks)

@@ -1,8 +1,8 @@
-"""The host arrays behind an mk_outputs (include/mk.h) and their way back to the caller's layouts:
-one table of field -> shape serves Session.outputs and meta_fit_node."""
+"""The host arrays behind an mk_outputs and an mk_diagnostics (include/mk.h) and their way back to the
+caller's layouts: one table of field -> shape serves Session.outputs and meta_fit_node."""
 import numpy as np
 
-from ._lib import N_LEVELS, Outputs, dptr
+from ._lib import N_DIAG, N_LEVELS, Diagnostics, Outputs, dptr
 
 # The array libmk fills for each mk_outputs field, row-major, in terms of: K subsets, P parameters,
 # C = q n_test kriging columns, L levels, n = n_samples, kept states, B amcmc batches, R = P + 1
@@ -20,6 +20,19 @@ SHAPES = {
     "p_pred_samples": ("K", "kept", "C"),
     "p_predict_sum": ("C", "L"),
 }
+# The same for the fields of mk_diagnostics (D = 3 rows: ess, mcse, rhat), keyed by the name the
+# callers see: "<field>_diag" per subset, "<field>_diag_worst" over the call's subsets.
+DIAG_SHAPES = {
+    "parameters_diag": ("K", "P", "D"),       # -> K x (3 x P)
+    "w_predict_diag": ("K", "C", "D"),        # -> K x (3 x q n_test)
+    "p_predict_diag": ("K", "C", "D"),
+    "parameters_diag_worst": ("P", "D"),      # -> 3 x P
+    "w_predict_diag_worst": ("C", "D"),       # -> 3 x q n_test
+    "p_predict_diag_worst": ("C", "D"),
+}
+# which struct a field belongs to, and its member there
+STRUCT_OF = {**{f: ("outputs", f) for f in SHAPES},
+             **{f: ("diagnostics", f.replace("_diag", "")) for f in DIAG_SHAPES}}
 
 
 class OutputBuffers:
@@ -40,6 +53,7 @@ class OutputBuffers:
         for f, a in self.buf.items():
             setattr(self.c, f, dptr(a))
 
+
     def _unpack(self, a):
         if a.ndim == 3:
             return [a[i].T.copy() for i in range(self.K)]
@@ -54,3 +68,25 @@ class OutputBuffers:
 
     def unpack(self):
         return {f: self._unpack(a) for f, a in self.buf.items()}
+
+
+class DiagnosticBuffers(OutputBuffers):
+    """The same for the requested `fields` of DIAG_SHAPES: `.c` is the mk_diagnostics pointing at the
+    arrays, unpack() the per-subset lists of 3 x C arrays and the 3 x C worst arrays."""
+
+    def __init__(self, K, cfg, n_test, fields):
+        unknown = set(fields) - set(DIAG_SHAPES)
+        if unknown:
+            raise KeyError(f"unknown diagnostics fields {sorted(unknown)}")
+        self.K = int(K)
+        dims = dict(K=self.K, P=cfg.P, C=cfg.q * int(n_test), D=N_DIAG)
+        self.buf = {f: np.zeros(tuple(dims[d] for d in shape)) for f, shape in DIAG_SHAPES.items() if f in fields}
+        self.c = self.struct(self.buf)
+
+    def struct(self, fields):
+        """An mk_diagnostics pointing at the arrays of `fields` only (the rest NULL)."""
+        c = Diagnostics()
+        for f in fields:
+            if f in self.buf:
+                setattr(c, STRUCT_OF[f][1], dptr(self.buf[f]))
+        return c

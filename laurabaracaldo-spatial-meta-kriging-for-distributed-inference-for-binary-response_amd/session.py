@@ -10,7 +10,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import Config, Problem, check, dptr, iptr
-from .outbuf import OutputBuffers
+from .outbuf import DiagnosticBuffers, OutputBuffers
 
 COV_MODELS = {"exponential": _lib.MK_COV_EXPONENTIAL, "matern": _lib.MK_COV_MATERN}
 LINKS = {"logit": _lib.MK_LINK_LOGIT, "probit": _lib.MK_LINK_PROBIT}
@@ -18,6 +18,7 @@ LINKS = {"logit": _lib.MK_LINK_LOGIT, "probit": _lib.MK_LINK_PROBIT}
 # kernel-stat ids (mk_session.hpp)
 (KS_CHOL_UPDATE, KS_CHOL_DIAG, KS_CHOL_TRSM, KS_SWEEP, KS_LAUUM, KS_ITER, KS_INV, KS_CHOL_UPDATE_SUB, KS_UPDATE_BUSY,
  KS_PRED_VAR, KS_COV, KS_SWEEP_FALLBACK, KS_KRIG_CHEB, KS_KRIG_FALLBACK) = range(14)
+KS_DIAG = 14      # the chain-diagnostic launches (always timed; 0 launches unless diagnostics were asked for)
 
 
 def _f64(a):
@@ -228,10 +229,33 @@ class Session:
         device-resident combine's input, no host round trip."""
         check(self._lib.mk_session_grids(self._h, int(which), ctypes.c_void_p(int(out_ptr)), 1))
 
-    def tile_grids(self, t0, prob=False):
+    def _diag_buffers(self, draws=True):
+        """Buffers for every diagnostics field this session can fill: the parameters and, with draws,
+        the w draws when it has test sites and the p draws when it also has their covariates."""
+        kinds = ["parameters"] + (["w_predict"] if draws and self.n_test else []) + \
+            (["p_predict"] if draws and self.n_test and self.x_test is not None else [])
+        return DiagnosticBuffers(self.S, self.cfg, self.n_test, {k + sfx for k in kinds for sfx in ("_diag", "_diag_worst")})
+
+    def tile_grids(self, t0, prob=False, diagnostics=False):
         """Tiled session (predict_tile > 0), after the run: (S, 200, q*Tc) w.predict grids of test
         sites [t0, t0 + Tc) -- one tile's kriging replay only (configs[4]'s per-tile combine).
-        prob=True: (w grids, p.predict grids) of the same replay (needs x_test)."""
+        prob=True: (w grids, p.predict grids) of the same replay (needs x_test).
+        diagnostics=True: the return value gains a last element, the dict of this tile's chain
+        diagnostics from the same replay -- 'w_predict_diag' (per subset 3 x q*Tc: ess, mcse, rhat),
+        'w_predict_diag_worst' (3 x q*Tc) and, with x_test, the 'p_predict_*' pair."""
+        if diagnostics:
+            db = self._diag_buffers()
+            sink = [f for f in db.buf if not f.startswith("parameters")]
+            check(self._lib.mk_session_set_diagnostics(self._h, ctypes.byref(db.struct(sink))))
+            try:
+                res = self.tile_grids(t0, prob=prob)
+            finally:
+                check(self._lib.mk_session_set_diagnostics(self._h, None))
+            c0 = int(t0) * self.q
+            c1 = c0 + self.q * min(self.predict_tile, self.n_test - int(t0))
+            d = {f: ([a[:, c0:c1] for a in v] if isinstance(v, list) else v[:, c0:c1])
+                 for f, v in db.unpack().items() if f in sink}
+            return (res if isinstance(res, tuple) else (res,)) + (d,)
         T = self.predict_tile
         Tc = min(T, self.n_test - int(t0))
         out = np.zeros((self.S, self.q * Tc, _lib.N_LEVELS))
@@ -291,12 +315,19 @@ class Session:
         return dict(launches=n.value, ms=ms.value, flops=fl.value)
 
     def outputs(self, quantiles=True, samples=False, w_samples=False, w_pred_samples=False, acceptance=False,
-                w_predict_sum=False, w_predict=True, p_predict=None, p_pred_samples=False, p_predict_sum=False):
+                w_predict_sum=False, w_predict=True, p_predict=None, p_pred_samples=False, p_predict_sum=False,
+                diagnostics=False):
         """quantiles: obj[[i]]$parameters (and $w.predict unless w_predict=False -- at 1M test sites the
         per-subset grids are 1.6 GB each; w_predict_sum gives this shard's term of the combine).
         p_predict / p_pred_samples / p_predict_sum: the same three of p(y = 1) = linkinv(x.test beta + w)
         per kept state (they need x_test); p_predict defaults to on when quantiles is and the session has
-        covariates."""
+        covariates.
+        diagnostics: adds the chain diagnostics of the kept states (the kept window when one is set) --
+        'parameters_diag', 'w_predict_diag', 'p_predict_diag': per subset 3 x C arrays, rows ess (Geyer's
+        initial monotone sequence), mcse (of the column mean) and split R-hat -- and the three
+        '*_diag_worst' arrays (3 x C: min ess, max mcse, max rhat over the subsets).  A tiled session
+        diagnoses each tile's draws from the replay that makes its grids; diagnostics="parameters"
+        leaves the kriging draws out."""
         have = bool(self.n_test)       # the w outputs are simply absent without test sites
         if p_predict is None:
             p_predict = bool(quantiles) and self.x_test is not None and have
@@ -305,9 +336,28 @@ class Session:
                   w_predict_sum=w_predict_sum and have, p_predict=p_predict, p_pred_samples=p_pred_samples,
                   p_predict_sum=p_predict_sum)
         kept = self.cfg.kept if self._window is None else self._window
-        ob = OutputBuffers(self.S, self.cfg, self.n_part, self.n_test, kept, {f for f, v in on.items() if v})
-        check(self._lib.mk_session_outputs(self._h, ctypes.byref(ob.c)))
-        return ob.unpack()
+        fields = {f for f, v in on.items() if v}
+        if not diagnostics:
+            ob = OutputBuffers(self.S, self.cfg, self.n_part, self.n_test, kept, fields)
+            check(self._lib.mk_session_outputs(self._h, ctypes.byref(ob.c)))
+            return ob.unpack()
+        db = self._diag_buffers(draws=diagnostics != "parameters")
+        sink = [f for f in db.buf if not f.startswith("parameters")] if self.predict_tile else []
+        replays = {"w_predict", "w_pred_samples", "w_predict_sum", "p_predict", "p_pred_samples", "p_predict_sum"}
+        extra = {"w_predict_sum"} if sink and not (fields & replays) else set()    # the sink needs the tile replays
+        ob = OutputBuffers(self.S, self.cfg, self.n_part, self.n_test, kept, fields | extra)
+        if sink:
+            check(self._lib.mk_session_set_diagnostics(self._h, ctypes.byref(db.struct(sink))))
+        try:
+            check(self._lib.mk_session_outputs(self._h, ctypes.byref(ob.c)))
+        finally:
+            if sink:
+                check(self._lib.mk_session_set_diagnostics(self._h, None))
+        direct = db.struct([f for f in db.buf if f not in sink])
+        check(self._lib.mk_session_diagnostics(self._h, ctypes.byref(direct)))
+        out = {f: v for f, v in ob.unpack().items() if f in fields}
+        out.update(db.unpack())
+        return out
 
     def close(self):
         if getattr(self, "_h", None):
@@ -337,6 +387,21 @@ def combine(grids, device=0, mean=True):
     fn = lib.mk_combine if mean else lib.mk_combine_sum
     check(fn(dptr(g.reshape(K, -1)), K, int(np.prod(g.shape[1:])), dptr(out), int(device)))
     return out
+
+
+def chain_diagnostics(x, axis=0, device=0):
+    """ess, mcse and split R-hat of caller-given chains on the device (mk_chain_diagnostics; the
+    kernel the sessions use).  x: 2-d, time along `axis`, one chain per index of the other axis (a
+    coda mcmc matrix such as p.beta.theta.samples is axis=0; p.w.samples is axis=1).  Returns 3 x C."""
+    lib = _lib.load()
+    x = np.asarray(x, dtype=np.float64)
+    if x.ndim != 2:
+        raise ValueError("error: chain_diagnostics takes a 2-d array")
+    chains = _f64(x.T if axis in (0, -2) else x)             # one contiguous chain per row
+    C, n = chains.shape
+    out = np.zeros((C, _lib.N_DIAG))
+    check(lib.mk_chain_diagnostics(dptr(chains), int(n), int(C), dptr(out), int(device)))
+    return out.T.copy()
 
 
 def correlation_batched(coords, phi, nu=None, cov_model="exponential", device=0):

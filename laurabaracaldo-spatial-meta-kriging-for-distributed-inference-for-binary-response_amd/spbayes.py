@@ -127,11 +127,31 @@ def spMvGLM(formula, coords, weights, starting, tuning, priors, amcmc, cov_model
     return fit
 
 
-def spPredict(sp_obj, pred_coords, pred_covars=None, start=1, end=None, thin=1):
+def spDiagnostics(sp_obj, start=1, end=None):
+    """Chain diagnostics of p.beta.theta.samples over iterations start..end (1-based, inclusive; the
+    window a coda user would pass to window()): a 3 x P array, rows ess (Geyer's initial monotone
+    sequence), mcse (of the column mean) and split R-hat, computed on the device from the chain the
+    fit recorded.  spMvGLM records from iteration 1, so start is where the caller's burn-in ends."""
+    ses = sp_obj.get("_session")
+    if ses is None:
+        raise ValueError("error: the spMvGLM fit was closed; spDiagnostics needs its recorded chain")
+    n_samples = sp_obj["_n_samples"]
+    end = n_samples if end is None else int(end)
+    start = int(start)
+    if not (1 <= start <= end <= n_samples):
+        raise ValueError("error: invalid start/end")
+    ses.set_kept_window(start, end)
+    return ses.outputs(quantiles=False, diagnostics="parameters")["parameters_diag"][0]
+
+
+def spPredict(sp_obj, pred_coords, pred_covars=None, start=1, end=None, thin=1, diagnostics=False):
     """p.w.predictive.samples ((q n_test) x kept) for kept iterations start..end (1-based,
     inclusive; every thin-th), kriged from the chain states spMvGLM recorded (no refit).
     With pred_covars ((q n_test) x p, location-major rows) also p.y.predictive.samples: spBayes's
-    binomial prediction linkinv(x(s)' beta + w(s)), beta and w(s) of the same iteration."""
+    binomial prediction linkinv(x(s)' beta + w(s)), beta and w(s) of the same iteration.
+    diagnostics=True: also "w.predictive.diagnostics" and, with covariates, "y.predictive.diagnostics"
+    (3 x (q n_test): ess, mcse, split R-hat per site) of the draws of iterations start..end, every one
+    of them (thin only picks what is returned), from the replay that makes the draws."""
     ses = sp_obj.get("_session")
     if ses is None:
         raise ValueError("error: the spMvGLM fit was closed; spPredict needs its recorded chain states")
@@ -147,9 +167,14 @@ def spPredict(sp_obj, pred_coords, pred_covars=None, start=1, end=None, thin=1):
             raise ValueError("error: pred.covars must have one row per prediction site and outcome (q * n rows)")
     ses.set_test_sites(ct, x_test=pred_covars)
     ses.set_kept_window(start, end)
-    out = ses.outputs(quantiles=False, w_pred_samples=True, p_pred_samples=pred_covars is not None)
+    out = ses.outputs(quantiles=False, w_pred_samples=True, p_pred_samples=pred_covars is not None,
+                      diagnostics=diagnostics)
     wp = out["w_pred_samples"][0]                  # (q n_test) x (end - start + 1)
     res = {"p.w.predictive.samples": wp[:, ::int(thin)]}
     if pred_covars is not None:
         res["p.y.predictive.samples"] = out["p_pred_samples"][0][:, ::int(thin)]
+    if diagnostics:
+        res["w.predictive.diagnostics"] = out["w_predict_diag"][0]
+        if pred_covars is not None:
+            res["y.predictive.diagnostics"] = out["p_predict_diag"][0]
     return res

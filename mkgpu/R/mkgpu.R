@@ -73,12 +73,16 @@ mk_glm_start <- function(y, x, weight, link = c("logit", "probit"), device = NUL
 # "combined", which mk_combine(obj) returns without recomputing.  With x.test ((q n_test) x p, the
 # covariates MK.R:87 hands spPredict) every obj[[k]] also holds p.predict (200 x q n_test: the
 # 200-level grid of p(y = 1) = linkinv(x.test beta + w) over the kept iterations) and "combined"
-# holds result3, their combination.
+# holds result3, their combination.  diagnostics = TRUE adds the numerical counterpart of the trace
+# plots (MK.R:147-149): every obj[[k]] also holds diagnostics = list(parameters = 3 x P, w.predict,
+# p.predict = 3 x q n_test) -- rows ess (Geyer's initial monotone sequence), mcse (of the column mean)
+# and split R-hat of its kept chain -- and attribute "diagnostics" holds the worst rows over the K
+# subsets (parameters.worst, w.predict.worst, p.predict.worst: min ess, max mcse, max rhat per column).
 mk_meta_fit <- function(y, x, weight, q, n.part, index.part, coords, coords.test,
                         n.batch = 100, batch.length = 50, accept.rate = 0.43,
                         cov.model = c("exponential", "matern"), link = c("logit", "probit"),
                         predict.tile = 0L, devices = 0L, glm.on.device = FALSE, n.report = 10,
-                        combine = c("mean", "median"), x.test = NULL) {
+                        combine = c("mean", "median"), x.test = NULL, diagnostics = FALSE) {
   cov.model <- match.arg(cov.model)
   link <- match.arg(link)
   combine <- match.arg(combine)
@@ -101,7 +105,8 @@ mk_meta_fit <- function(y, x, weight, q, n.part, index.part, coords, coords.test
                unlist(lapply(index.part, function(i) as.vector(x[.mk_rows(i, q), , drop = FALSE] * 1.0))),
                coords.test, x.test, as.integer(q), ncol(x), cfg,
                floor(runif(1) * 2^52),                                               # honours set.seed
-               as.integer(devices), as.integer(n.report), as.integer(combine == "median"))
+               as.integer(devices), as.integer(n.report), as.integer(combine == "median"),
+               isTRUE(diagnostics))
   P <- length(res[[1]]) / (S * 200)
   C <- length(res[[2]]) / (S * 200)
   obj <- lapply(seq_len(S), function(k) {
@@ -110,9 +115,18 @@ mk_meta_fit <- function(y, x, weight, q, n.part, index.part, coords, coords.test
       w.predict = matrix(res[[2]][(k - 1) * 200 * C + seq_len(200 * C)], 200, C),
       acceptance = matrix(res[[3]][(k - 1) * n.batch * (P + 1) + 1:(n.batch * (P + 1))], n.batch, P + 1))
     if (!is.null(res[[6]])) o$p.predict <- matrix(res[[6]][(k - 1) * 200 * C + seq_len(200 * C)], 200, C)
+    dg <- res[[8]]
+    if (!is.null(dg)) {
+      rows <- c("ess", "mcse", "rhat")
+      one <- function(a, n) if (is.null(a)) NULL else matrix(a[(k - 1) * 3 * n + seq_len(3 * n)], 3, n, dimnames = list(rows, NULL))
+      o$diagnostics <- list(parameters = one(dg[[1]], P), w.predict = one(dg[[2]], C), p.predict = one(dg[[3]], C))
+    }
     o
   })
   attr(obj, "combined") <- list(result = res[[4]], result2 = res[[5]], result3 = res[[7]], method = combine)
+  if (!is.null(res[[8]]))
+    attr(obj, "diagnostics") <- list(parameters.worst = res[[8]][[4]], w.predict.worst = res[[8]][[5]],
+                                     p.predict.worst = res[[8]][[6]])
   obj
 }
 

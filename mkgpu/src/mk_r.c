@@ -2,8 +2,9 @@
  * installed there); see INTEGRATION.md for how each entry replaces a reference line.
  *
  *   mk_r_fit        -> mk_meta_fit               MK.R:100-133 (makeCluster + foreach %dopar%
- *                                                partitioned_spMvGLM over the node's GPUs, and the
- *                                                quantile-average combine, device to device)
+ *                      / mk_meta_fit_diag        partitioned_spMvGLM over the node's GPUs, and the
+ *                                                quantile-average combine, device to device; with
+ *                                                diagnostics = TRUE the chains' ess / mcse / R-hat)
  *   mk_r_spmvglm    -> mk_session_create / _run  MK.R:80-84 (spMvGLM of one subset; the session
  *                      / _outputs                stays alive for spPredict, owned by an external
  *                                                pointer whose finalizer destroys it)
@@ -122,9 +123,13 @@ static int n_params(const mk_config* c, int np, int q) {
  * x_test ((q n_test) x p, or NULL): MK.R:87's x.test; with it the grids of p(y = 1) too.
  * Returns list(parameters = S x 200 x P, w.predict = S x 200 x q n_test, acceptance,
  *              result = 200 x P, result2 = 200 x q n_test,
- *              p.predict = S x 200 x q n_test, result3 = 200 x q n_test (both NULL without x_test)). */
+ *              p.predict = S x 200 x q n_test, result3 = 200 x q n_test (both NULL without x_test),
+ *              diagnostics).
+ * diagnostics (logical): TRUE runs mk_meta_fit_diag and the last element is list(parameters = S x 3 x P,
+ * w.predict = S x 3 x q n_test, p.predict (NULL without x_test), parameters.worst = 3 x P, w.predict.worst,
+ * p.predict.worst = 3 x q n_test) -- rows ess, mcse, split R-hat of every kept chain; FALSE leaves it NULL. */
 SEXP mk_r_fit(SEXP n_part, SEXP coords, SEXP y, SEXP weights, SEXP x, SEXP coords_test, SEXP x_test, SEXP q, SEXP p,
-              SEXP cfg, SEXP seed, SEXP devices, SEXP report, SEXP combine) {
+              SEXP cfg, SEXP seed, SEXP devices, SEXP report, SEXP combine, SEXP diagnostics) {
   mk_problem pr;
   mk_config c;
   read_problem(n_part, coords, y, weights, x, coords_test, x_test, q, p, &pr);
@@ -156,8 +161,29 @@ SEXP mk_r_fit(SEXP n_part, SEXP coords, SEXP y, SEXP weights, SEXP x, SEXP coord
   cb.max_iter = 100;
   cb.tol = 1e-12;
   progress_t pg = {asInteger(report), c.n_batch, c.batch_length, 0};
-  if (mk_meta_fit(&pr, &c, INTEGER(devices), LENGTH(devices), r_progress, &pg, &o, &cb) != MK_OK) fail(7);
-  SEXP res = PROTECT(allocVector(VECSXP, 7));
+  const int diag = asLogical(diagnostics) == TRUE;
+  SEXP dgl = PROTECT(diag ? allocVector(VECSXP, 6) : R_NilValue);
+  mk_diagnostics dg;
+  memset(&dg, 0, sizeof dg);
+  if (diag) {   /* the list owns the arrays (protected through it) */
+    const int wp = pr.n_test > 0;
+    SET_VECTOR_ELT(dgl, 0, allocVector(REALSXP, (R_xlen_t)S * MK_N_DIAG * P));
+    SET_VECTOR_ELT(dgl, 1, wp ? allocVector(REALSXP, (R_xlen_t)S * MK_N_DIAG * C) : R_NilValue);
+    SET_VECTOR_ELT(dgl, 2, prob ? allocVector(REALSXP, (R_xlen_t)S * MK_N_DIAG * C) : R_NilValue);
+    SET_VECTOR_ELT(dgl, 3, allocMatrix(REALSXP, MK_N_DIAG, P));
+    SET_VECTOR_ELT(dgl, 4, wp ? allocMatrix(REALSXP, MK_N_DIAG, (int)C) : R_NilValue);
+    SET_VECTOR_ELT(dgl, 5, prob ? allocMatrix(REALSXP, MK_N_DIAG, (int)C) : R_NilValue);
+    dg.parameters = dp(VECTOR_ELT(dgl, 0));
+    dg.w_predict = dp(VECTOR_ELT(dgl, 1));
+    dg.p_predict = dp(VECTOR_ELT(dgl, 2));
+    dg.parameters_worst = dp(VECTOR_ELT(dgl, 3));
+    dg.w_predict_worst = dp(VECTOR_ELT(dgl, 4));
+    dg.p_predict_worst = dp(VECTOR_ELT(dgl, 5));
+  }
+  const int rc = diag ? mk_meta_fit_diag(&pr, &c, INTEGER(devices), LENGTH(devices), r_progress, &pg, &o, &cb, &dg)
+                      : mk_meta_fit(&pr, &c, INTEGER(devices), LENGTH(devices), r_progress, &pg, &o, &cb);
+  if (rc != MK_OK) fail(7);
+  SEXP res = PROTECT(allocVector(VECSXP, 8));
   SET_VECTOR_ELT(res, 0, par);
   SET_VECTOR_ELT(res, 1, wpr);
   SET_VECTOR_ELT(res, 2, acc);
@@ -165,7 +191,8 @@ SEXP mk_r_fit(SEXP n_part, SEXP coords, SEXP y, SEXP weights, SEXP x, SEXP coord
   SET_VECTOR_ELT(res, 4, r2);
   SET_VECTOR_ELT(res, 5, ppr);
   SET_VECTOR_ELT(res, 6, r3);
-  UNPROTECT(8);
+  SET_VECTOR_ELT(res, 7, dgl);
+  UNPROTECT(9);
   return res;
 }
 
@@ -326,7 +353,7 @@ SEXP mk_r_shutdown(void) {
 }
 
 static const R_CallMethodDef call_methods[] = {
-    {"mk_r_fit", (DL_FUNC)&mk_r_fit, 14},
+    {"mk_r_fit", (DL_FUNC)&mk_r_fit, 15},
     {"mk_r_spmvglm", (DL_FUNC)&mk_r_spmvglm, 8},
     {"mk_r_sppredict", (DL_FUNC)&mk_r_sppredict, 6},
     {"mk_r_combine", (DL_FUNC)&mk_r_combine, 4},

@@ -60,6 +60,10 @@ def main():
     ap.add_argument("--devices", default=None,
                     help="one process, libmk's multi-device driver (mk_meta_fit) over these HIP devices, e.g. "
                          "0,1,2,3,4,5,6,7 (a device may repeat: several shards on one GPU, device-copy exchange)")
+    ap.add_argument("--diagnostics", action="store_true",
+                    help="chain diagnostics (ess, mcse, split R-hat per kept chain, on the device): one more JSON "
+                         "line after the summary, {\"diagnostics\": convergence_report(...)}; one process (plain or "
+                         "--devices)")
     a = ap.parse_args()
     c = dict(CONFIGS[a.config])
     for k_arg, k_cfg in [("n", "n"), ("subsets", "K"), ("n_test", "n_test"), ("n_batch", "n_batch"),
@@ -71,6 +75,8 @@ def main():
         return node_main(a, c)
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
+    if a.diagnostics and world > 1:
+        ap.error("--diagnostics runs in one process: plain, or over several GPUs with --devices")
     local = int(os.environ.get("LOCAL_RANK", "0"))
     dist = None
     if world > 1:
@@ -112,12 +118,16 @@ def main():
         t3 = time.perf_counter()
         # 1M sites (tiled kriging): the parameter grids now; w.predict tile by tile in the combine
         # one process: the grids to the host for the combine; N > 1: they stay in HBM (shard_grids below)
-        out = ses.outputs(quantiles=True, w_predict=not big) if world == 1 else {"parameters": [], "w_predict": []}
+        # --diagnostics: with the grids when the kriging is fused; tiled: the parameters now, the draws tile by tile
+        dg = ("parameters" if big else True) if a.diagnostics else False
+        out = (ses.outputs(quantiles=True, w_predict=not big, diagnostics=dg) if world == 1
+               else {"parameters": [], "w_predict": []})
     else:                                         # K < world: this rank has no subsets, it joins the exchange
         t3 = time.perf_counter()
         out = {"parameters": [], "w_predict": []}
     t["fit_s"] = t3 - t2
     t["predict_quantiles_s"] = time.perf_counter() - t3
+    diag = {k: v for k, v in out.items() if "_diag" in k}
 
     t4 = time.perf_counter()
     result3 = None
@@ -162,8 +172,14 @@ def main():
         result = mk.combine_results([{"parameters": g} for g in out["parameters"]], device=local,
                                     method=a.combine)[0]
         result2 = np.zeros((200, C))
+        if a.diagnostics:    # the worst rows over the subsets, filled tile by tile from each tile's own replay
+            diag["w_predict_diag_worst"] = np.zeros((3, C))
         for t0 in range(0, c["n_test"], tile):
-            g = tile_grids(t0)
+            if a.diagnostics:
+                g, dt = ses.tile_grids(t0, diagnostics=True)
+                diag["w_predict_diag_worst"][:, t0 * q:t0 * q + g.shape[2]] = dt["w_predict_diag_worst"]
+            else:
+                g = tile_grids(t0)
             result2[:, t0 * q:t0 * q + g.shape[2]] = mk.combine_results([{"parameters": x} for x in g], device=local,
                                                                         method=a.combine)[0]
             del g
@@ -191,6 +207,8 @@ def main():
             rec["truth_beta_phi"] = truth.tolist()
             rec.update(predictive_scores(result3, d))
         print(json.dumps(rec), flush=True)
+        if a.diagnostics:
+            print(json.dumps({"diagnostics": mk.convergence_report(diag)}), flush=True)
     if dist is not None:
         dist.destroy_process_group()
 
@@ -225,7 +243,8 @@ def node_main(a, c):
     ph, result, result2, summ, cfg = mk.metakriging.reference_flow(
         d, K, q, cov_model=c["cov"], n_batch=c["n_batch"], batch_length=c["batch_length"], seed=a.seed,
         devices=devices, method=a.combine, predict_tile=c.get("predict_tile", 0), partition_method=a.partition,
-        progress=progress, predictive=True)     # MK.R:87's x.test: the grids of p(y = 1) and result3
+        progress=progress, predictive=True,     # MK.R:87's x.test: the grids of p(y = 1) and result3
+        diagnostics=a.diagnostics)
     ph["data_s"] = data_s
     rec = dict(config=a.config, workload=c, devices=devices, combine=a.combine, phases=ph,
                subset_iters_per_s=K * cfg.n_samples / ph["chains_s"])
@@ -237,6 +256,8 @@ def node_main(a, c):
     rec["truth_beta_phi"] = truth.tolist()
     rec.update(predictive_scores(summ.get("result3"), d))
     print(json.dumps(rec), flush=True)
+    if a.diagnostics:
+        print(json.dumps({"diagnostics": mk.convergence_report(summ["diagnostics"])}), flush=True)
 
 
 if __name__ == "__main__":
