@@ -129,6 +129,12 @@ int32_t mk_session_predict_tile(const mk_session* s);
  * baseline of bench.py times the oracle over the window the device timed.) */
 int mk_session_chain_state(mk_session* s, int32_t subset, double* beta, double* theta, double* w, double* tune,
                            double* accept);
+/* Failure semantics of the factorisations.  mk_session_create
+ * returns MK_E_ARG, naming the subset, when a subset has a non-finite coordinate or two sites at the
+ * same coordinates, or when a correlation matrix at the starting values meets a pivot that is not
+ * > 0.  In the chain a phi / nu candidate whose factorisation meets such a pivot is a rejection;
+ * out [n_subsets * q] (subset-major) receives how many each (subset, outcome) pair has had so far. */
+int mk_session_notpd_counts(mk_session* s, int64_t* out);
 /* Launch schedule (results are the same chain either way): mode 1 = lookahead
  * (the next iteration's phi candidates are factored while this iteration's inverse and latent
  * sweep run; Matern: the nu step follows the phi decision; n_streams <= 1), 0 = sequential, -1 = default (lookahead where
@@ -361,7 +367,9 @@ int mk_r_sample_replace(int32_t seed, int32_t n, int32_t size, int32_t* out);
  * Temme/CF2 Bessel-K evaluation) -- the covariance-assembly arithmetic the chains use. */
 int mk_correlation_batched(const double* coords, int32_t S, int32_t n, const double* phi, const double* nu,
                            int32_t cov_model, double* R_out, int32_t device);
-/* Cholesky (lower) + log-determinant (+ optional inverse) of S SPD n x n matrices. */
+/* Cholesky (lower) + log-determinant (+ optional inverse) of S SPD n x n matrices.  MK_E_ARG when a
+ * factorisation meets a pivot that is not > 0 (negative, zero or NaN); mk_last_error then reads
+ * "matrix <i> is not positive definite", i the lowest index of such a matrix. */
 int mk_cholesky_batched(const double* A, int32_t S, int32_t n, double* L_out, double* logdet_out,
                         double* inv_out, int32_t device);
 

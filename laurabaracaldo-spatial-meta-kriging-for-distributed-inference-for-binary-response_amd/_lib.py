@@ -94,6 +94,7 @@ EXPORTS = {
     "mk_session_iteration": (ctypes.c_int32, [ctypes.c_void_p]),
     "mk_session_predict_tile": (ctypes.c_int32, [ctypes.c_void_p]),
     "mk_session_chain_state": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, _dp, _dp, _dp, _dp, _dp]),
+    "mk_session_notpd_counts": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64)]),
     "mk_session_set_lookahead": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32]),
     "mk_session_lookahead": (ctypes.c_int32, [ctypes.c_void_p]),
     "mk_session_outputs": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(Outputs)]),

@@ -13,12 +13,14 @@
 #include <hip/hip_runtime.h>
 #include <dirent.h>
 #include <unistd.h>
+#include <algorithm>
 #include <atomic>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <memory>
+#include <numeric>
 #include <string>
 #include <vector>
 #include "mk_session.hpp"
@@ -101,6 +103,7 @@ Model model_view(const Model& m, int s0, int S) {
   v.ld_part = m.ld_part + (long)s * m.q * m.nt;   // per (subset, outcome) pair
   v.quad_c = m.quad_c + (long)s * m.q;
   v.info = m.info + (long)s * m.q;
+  v.notpd = m.notpd + (long)s * m.q;
   v.sw_delta = m.sw_delta + s * Np;
   v.sw_dll = m.sw_dll + s * Np;
   v.sw_logu = m.sw_logu + s * Np;
@@ -169,6 +172,37 @@ mk_session::~mk_session() {
   (void)hipGetLastError();   // teardown errors are not the next call's
 }
 
+// What no starting value can factor: a subset with a non-finite coordinate (R is NaN), or with two
+// sites at the same place (rho(0) = 1 exactly: two equal rows, R singular at every phi and nu).  The
+// device flag (initial_state) sees such a start only where the pivot comes out <= 0 or NaN; a
+// duplicate deep in the ordering can leave a pivot of +1e-16 and a finite, meaningless factor.
+// Sites sorted by (x, y) per subset; subsets are named by their global index.
+static int check_sites(const mk_problem* pr) {
+  long off = 0;
+  std::vector<int> ord;
+  for (int i = 0; i < pr->n_subsets; ++i) {
+    const int ns = pr->n_part[i];
+    const double *x = pr->coords + 2 * off, *y = x + ns;
+    const std::string who = "subset " + std::to_string(pr->subset_base + i);
+    for (int r = 0; r < ns; ++r)
+      if (!std::isfinite(x[r]) || !std::isfinite(y[r]))
+        return set_err(MK_E_ARG, who + ": site " + std::to_string(r) + " has a non-finite coordinate");
+    ord.resize(ns);
+    std::iota(ord.begin(), ord.end(), 0);
+    std::sort(ord.begin(), ord.end(), [&](int a, int b) {
+      return x[a] != x[b] ? x[a] < x[b] : (y[a] != y[b] ? y[a] < y[b] : a < b);
+    });
+    for (int k = 1; k < ns; ++k) {
+      const int a = ord[k - 1], b = ord[k];
+      if (x[a] == x[b] && y[a] == y[b])
+        return set_err(MK_E_ARG, who + ": sites " + std::to_string(a) + " and " + std::to_string(b) +
+                                     " have the same coordinates (a singular correlation matrix)");
+    }
+    off += ns;
+  }
+  return 0;
+}
+
 static int check_cfg(const mk_problem* pr, const mk_config* c) {
   if (!pr || !c) return set_err(MK_E_ARG, "null problem/config");
   if (pr->n_subsets < 1) return set_err(MK_E_ARG, "n_subsets must be >= 1");
@@ -197,7 +231,7 @@ static int check_cfg(const mk_problem* pr, const mk_config* c) {
     if (!(c->phi_unif_a[h] < c->phi_starting[h] && c->phi_starting[h] < c->phi_unif_b[h]))
       return set_err(MK_E_ARG, "phi starting value outside phi.Unif support");
   }
-  return 0;
+  return check_sites(pr);
 }
 
 // Work lists for `ng` run groups + the whole-shard view (last): list/plist per pair, 2 counts per view.
@@ -371,7 +405,8 @@ static int alloc_chain_state(mk_session* s, const mk_problem* pr) {
       (rc = s->alloc(&md.quad, (size_t)S * q)) || (rc = s->alloc(&md.A_full, (size_t)S * q * q)) ||
       (rc = s->alloc(&md.Ainv, (size_t)S * q * q)) || (rc = s->alloc(&md.dirty, (size_t)S * q)) ||
       (rc = s->alloc(&md.ld_part, (size_t)S * q * nt)) || (rc = s->alloc(&md.quad_c, (size_t)S * q)) ||
-      (rc = s->alloc(&md.info, (size_t)S * q)) || (rc = s->alloc(&md.sw_delta, (size_t)S * Np)) ||
+      (rc = s->alloc(&md.info, (size_t)S * q)) || (rc = s->alloc(&md.notpd, (size_t)S * q)) ||
+      (rc = s->alloc(&md.sw_delta, (size_t)S * Np)) ||
       (rc = s->alloc(&md.sw_dll, (size_t)S * Np)) || (rc = s->alloc(&md.sw_logu, (size_t)S * Np)) ||
       (rc = s->alloc(&md.sw_acc, (size_t)S * Np)) || (rc = s->alloc(&md.samples, (size_t)S * n_samples * P)) ||
       (rc = s->alloc(&md.acc_hist, (size_t)S * md.n_batch * (o_w + 1))))
@@ -588,6 +623,7 @@ static int starting_values(mk_session* s, const mk_config* c) {
   HIPCHK(hipMemcpy(md.Ainv, hAi.data(), hAi.size() * 8, hipMemcpyHostToDevice));
   HIPCHK(hipMemsetAsync(md.acc, 0, (size_t)S * n_mh_max * 8, s->stream));
   HIPCHK(hipMemsetAsync(md.dirty, 0, (size_t)S * q * 4, s->stream));
+  HIPCHK(hipMemsetAsync(md.notpd, 0, (size_t)S * q * sizeof(long long), s->stream));
   HIPCHK(hipMemsetAsync(md.u, 0, (size_t)S * q * n_pad * 8, s->stream));
   HIPCHK(hipMemsetAsync(md.z, 0, (size_t)S * q * n_pad * 8, s->stream));
   HIPCHK(hipMemsetAsync(md.Z, 0, (size_t)S * q * q * n_pad * 8, s->stream));
@@ -622,6 +658,19 @@ static int initial_state(mk_session* s) {
   MK_LAUNCH(k_init_state, dim3(S), dim3(256), 0, s->stream, md);
   launch_candidates(md, ms, s->stream, S * q, 0, q, 2, 0);
   launch_cholesky(s, a, 0, q);
+  // a start that cannot be factored is an error, not a chain: every later candidate would be compared
+  // with a NaN logdetR / quad.  info[] is zero past this point (k_theta_init leaves it alone).
+  {
+    std::vector<int> info((size_t)S * q);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(s->stream));
+    HIPCHK(hipMemcpy(info.data(), md.info, info.size() * sizeof(int), hipMemcpyDeviceToHost));
+    for (int sh = 0; sh < S * q; ++sh)
+      if (info[sh])
+        return set_err(MK_E_ARG, "subset " + std::to_string(md.subset_base + sh / q) + ", outcome " + std::to_string(sh % q) +
+                                     ": the correlation matrix at the starting values is not positive definite "
+                                     "(coincident or non-finite sites?)");
+  }
   MK_LAUNCH(k_theta_init, dim3((S * q + 63) / 64), dim3(64), 0, s->stream, md, ms, 0, q);
   MK_LAUNCH(k_dirty_list, dim3(1), dim3(256), 0, s->stream, md, 0, a.d_list, a.d_count, a.d_plist, a.d_pcount);
   launch_inverse(s, a);
@@ -798,6 +847,18 @@ extern "C" int mk_session_chain_state(mk_session* s, int32_t subset, double* bet
   if (w) HIPCHK(hipMemcpy(w, md.w + i * md.Np, (size_t)nq * 8, hipMemcpyDeviceToHost));
   if (tune) HIPCHK(hipMemcpy(tune, md.tune + i * md.n_mh_max, (size_t)nmh * 8, hipMemcpyDeviceToHost));
   if (accept) HIPCHK(hipMemcpy(accept, md.acc + i * md.n_mh_max, (size_t)nmh * 8, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+// Per (subset, outcome): the phi / nu candidates rejected so far because their factorisation met a
+// pivot that is not > 0 (k_theta_mh counts where it reads the flag).
+extern "C" int mk_session_notpd_counts(mk_session* s, int64_t* out) {
+  if (!s || !out) return set_err(MK_E_ARG, "null session/output");
+  if (s->poisoned) return set_err(MK_E_HIP, std::string("session unusable after an earlier failure: ") + s->poisoned);
+  MK_ENTRY_DEVICE(s->device);
+  static_assert(sizeof(long long) == sizeof(int64_t), "notpd counts are 64-bit");
+  HIPCHK(hipStreamSynchronize(s->stream));
+  HIPCHK(hipMemcpy(out, s->md.notpd, (size_t)s->S * s->q * sizeof(int64_t), hipMemcpyDeviceToHost));
   return 0;
 }
 

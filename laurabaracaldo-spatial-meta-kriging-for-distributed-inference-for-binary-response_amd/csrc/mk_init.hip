@@ -24,7 +24,8 @@ __global__ __launch_bounds__(256) void k_init_state(Model md) {
     }
 }
 
-// Accept the starting-value factorisations of outcomes h0 .. h0+hc-1 unconditionally.
+// Accept the starting-value factorisations of outcomes h0 .. h0+hc-1.  The host has read info[] (all
+// zero) before this launch; the kernel leaves it alone.
 __global__ __launch_bounds__(64) void k_theta_init(Model md, MatSet ms, int h0, int hc) {
   const int e = blockIdx.x * 64 + threadIdx.x;
   if (e >= md.S * hc) return;
@@ -36,7 +37,6 @@ __global__ __launch_bounds__(64) void k_theta_init(Model md, MatSet ms, int h0, 
   md.quad[sh] = md.quad_c[sh];
   ms.cur[sh] ^= 1;
   md.dirty[sh] = 1;
-  md.info[sh] = 0;
 }
 
 // Copy S dense n x n matrices into the candidate slot, identity-padded, zero border row.

@@ -216,6 +216,17 @@ static int tile_outputs(mk_session* s, int t0, double* dq, double* dqp, mk_outpu
     if (rc) return rc;
   }
   HIPCHK(hipStreamSynchronize(st));
+  // The replay factored the kept states again.  Each was an accepted candidate of the fit, so a flag
+  // here means the device disagreed with itself: an error (the draws above came from a NaN factor),
+  // and the flag is cleared for the chain's next candidates.
+  std::vector<int> info((size_t)S * q);
+  HIPCHK(hipMemcpy(info.data(), md.info, info.size() * sizeof(int), hipMemcpyDeviceToHost));
+  for (int sh = 0; sh < S * q; ++sh)
+    if (info[sh]) {
+      HIPCHK(hipMemset(md.info, 0, info.size() * sizeof(int)));
+      return set_err(MK_E_HIP, "kriging replay: subset " + std::to_string(md.subset_base + sh / q) + ", outcome " +
+                                   std::to_string(sh % q) + ": a kept state's factorisation failed (it succeeded in the fit)");
+    }
   return 0;
 }
 
@@ -562,6 +573,9 @@ int mk::predict_tile(mk_session* s, int t0, double* dq, mk_outputs* o, double* d
   if ((dqp || (o && o->p_pred_samples)) && !s->d_xt) return set_err(MK_E_ARG, "predictive probabilities need x_test");
   if (s->diag_on && (s->diag_sink.p_predict || s->diag_sink.p_predict_worst) && !s->d_xt)
     return set_err(MK_E_ARG, "the diagnostics sink asks for p_predict: that needs x_test");
+  // the flag of a lookahead candidate that no iteration will decide on is not a kept state's
+  // (tile_outputs reads the flags after the replay)
+  HIPCHK(hipMemsetAsync(s->md.info, 0, (size_t)s->S * s->q * sizeof(int), s->stream));
   const int rc_cheb = predict_tile_cheb(s, t0, dq, o, dqp);
   if (rc_cheb != MK_CHEB_EXACT) return rc_cheb;
   Model& md = s->md;
@@ -575,6 +589,8 @@ int mk::predict_tile(mk_session* s, int t0, double* dq, mk_outputs* o, double* d
   Group g = s->all;
   s->la.next = -1;   // the replay factors into the free slots: a lookahead candidate is gone
   s->cov.pre = -1;   // and so is an early-assembled one
+  // nor is a flag of the interpolation nodes that sent this tile here
+  HIPCHK(hipMemsetAsync(md.info, 0, (size_t)S * q * sizeof(int), st));
   HIPCHK(hipMemsetAsync((void*)md.coords_test, 0, (size_t)2 * T_pad * 8, st));
   HIPCHK(hipMemcpyAsync((void*)md.coords_test, s->d_ct_all + t0, (size_t)Tc * 8, hipMemcpyDeviceToDevice, st));
   HIPCHK(hipMemcpyAsync((void*)(md.coords_test + T_pad), s->d_ct_all + s->n_test_pad_all + t0, (size_t)Tc * 8,

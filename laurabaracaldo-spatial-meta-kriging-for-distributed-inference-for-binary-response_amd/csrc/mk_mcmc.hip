@@ -250,7 +250,8 @@ __global__ __launch_bounds__(64) void k_theta_mh(Model md, MatSet ms, int h0, in
   const double qc = md.quad_c[sh];
   const double ratio = -0.5 * (ldc - md.logdetR[sh]) - 0.5 * (qc - md.quad[sh]) + unif_jacobian(v_c, a, b) -
                        unif_jacobian(v_cur, a, b);
-  const bool accept = md.info[sh] == 0 && lu <= ratio;
+  const bool flagged = md.info[sh] != 0;   // the factor did not exist: a rejection, and counted as one
+  const bool accept = !flagged && lu <= ratio;
   if (accept) {
     th[idx] = th_c;
     ms.cur[sh] ^= 1;
@@ -260,7 +261,10 @@ __global__ __launch_bounds__(64) void k_theta_mh(Model md, MatSet ms, int h0, in
     md.acc[(long)s * md.n_mh_max + j_mh] += 1.0;
   }
   if (which == 1 && md.la_nu) md.la_nu[sh] = accept ? 1 : 0;   // lookahead schedule: k_nu_border
-  md.info[sh] = 0;
+  if (flagged) {
+    md.notpd[sh] += 1;
+    md.info[sh] = 0;
+  }
 }
 
 // Compact lists (deterministic order) of (subset, outcome) pairs: list_inv = pairs whose

@@ -69,7 +69,7 @@ struct Model {
   // candidate scratch
   double* ld_part;   // [S*q][nt]   logdet partials of the candidate factor (per (subset, outcome) pair)
   double* quad_c;    // [S*q]
-  int* info;         // [S*q]
+  int* info;         // [S*q]       1: the candidate's factorisation met a pivot that is not > 0 (k_chol_diag)
   // sweep scratch
   double* sw_delta;  // [S][Np]
   double* sw_dll;    // [S][Np]
@@ -93,6 +93,9 @@ struct Model {
   double* zc;          // [S][q][n_pad]     z'_h = L'_h^-1 u_h of the candidate
   int* la_nu;          // [S*q]             Matern: 1 where this iteration's nu step accepted (k_nu_border)
   int P;               // reported columns
+  // candidates rejected for a set info flag since the chain started (k_theta_mh).  Last, so that no
+  // other field's offset in the kernels' arguments depends on it.
+  long long* notpd;    // [S*q]
 };
 
 struct MatSet {

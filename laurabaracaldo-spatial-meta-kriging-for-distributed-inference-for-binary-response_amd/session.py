@@ -203,6 +203,13 @@ class Session:
         st["iteration"] = self.iteration
         return st
 
+    def notpd_counts(self):
+        """(S, q) int64: per (subset, outcome), the phi / nu candidates rejected so far because their
+        Cholesky factorisation met a pivot that is not > 0 (mk_session_notpd_counts)."""
+        out = np.zeros((self.S, self.q), dtype=np.int64)
+        check(self._lib.mk_session_notpd_counts(self._h, out.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))))
+        return out
+
     def set_test_sites(self, coords_test, x_test=None):
         """Kriging sites for the next outputs() of a session created with predict_tile > 0
         (its kept chain states were recorded during the run): spPredict without refitting.

@@ -53,6 +53,60 @@ def test_no_gpu_errors_cleanly(mk):
     assert lib.mk_session_count() == 0             # nothing left behind by the failed create
 
 
+def _two_subsets(mk, q=1):
+    d = mk.synthetic.generate(100, q=q, n_test=0, seed=4)
+    p = 2 * q
+    subs = [dict(coords=d["coords"][i * 50:(i + 1) * 50].copy(), y=d["y"][i * 50 * q:(i + 1) * 50 * q],
+                 weights=np.ones(50 * q), x=d["x"][i * 50 * q:(i + 1) * 50 * q]) for i in range(2)]
+    return subs, mk.SamplerConfig(q, p, np.zeros(p), np.full(p, 0.1), n_batch=1, batch_length=2)
+
+
+@pytest.mark.parametrize("a,b", [(0, 1), (17, 41)])
+def test_create_refuses_two_sites_at_the_same_coordinates(mk, a, b):
+    """The argument check of mk_session_create runs before any device is touched: a subset whose R is
+    singular at every (phi, nu) is MK_E_ARG, naming the subset and the two sites (subset_base counts)."""
+    subs, cfg = _two_subsets(mk)
+    subs[1]["coords"][b] = subs[1]["coords"][a]
+    live = mk.load().mk_session_count()
+    with pytest.raises(mk.MkError) as e:
+        mk.Session(subs, cfg, subset_base=6)
+    assert e.value.code == -1
+    assert f"subset 7: sites {a} and {b} have the same coordinates" in str(e.value)
+    assert mk.load().mk_session_count() == live
+    subs2, cfg2 = _two_subsets(mk, q=2)                         # q = 2, and +0.0 / -0.0 are one place
+    subs2[0]["coords"][3] = (0.0, 0.25)
+    subs2[0]["coords"][30] = (-0.0, 0.25)
+    with pytest.raises(mk.MkError) as e:
+        mk.Session(subs2, cfg2)
+    assert e.value.code == -1 and "subset 0: sites 3 and 30 " in str(e.value)
+
+
+@pytest.mark.parametrize("bad", [np.nan, np.inf, -np.inf])
+def test_create_refuses_a_non_finite_coordinate(mk, bad):
+    subs, cfg = _two_subsets(mk)
+    subs[0]["coords"][49, 1] = bad
+    live = mk.load().mk_session_count()
+    with pytest.raises(mk.MkError) as e:
+        mk.Session(subs, cfg)
+    assert e.value.code == -1 and "subset 0: site 49 has a non-finite coordinate" in str(e.value)
+    assert mk.load().mk_session_count() == live
+
+
+def test_create_accepts_sites_that_share_one_coordinate(mk):
+    """Sites that share one coordinate only are different sites for the host check: the create goes on
+    to the device, and without one fails for that reason (MK_E_NODEV), not for its arguments.  (With a
+    device the session is created: tests/test_gpu_notpd.py.)"""
+    if mk.load().mk_device_count() > 0:
+        pytest.skip("GPU present")
+    subs, cfg = _two_subsets(mk)
+    x0, y0 = subs[0]["coords"][0]
+    subs[0]["coords"][1] = (x0, y0 + 1e-3)
+    subs[0]["coords"][2] = (x0 + 1e-3, y0)
+    with pytest.raises(mk.MkError) as e:
+        mk.Session(subs, cfg)
+    assert e.value.code == -4
+
+
 def test_partition_sizes_follow_reference(mk):
     n_part, idx = mk.partition(2003, 20, seed=3)
     assert list(n_part[:-1]) == [100] * 19 and n_part[-1] == 2003 - 100 * 19      # MK.R:17-18
