@@ -31,6 +31,13 @@
 // C^T: lane l, register r of block (bm,bn) is C[m = row0 + 16bm + (l&15)][n = col0 + 16bn +
 // (l>>4) + 4r] -- consecutive lanes walk consecutive rows of a column-major C
 // (coalesced 128-B stores) instead of consecutive columns.
+//
+// Two 128 x 128 bodies deal the 16-blocks over the waves differently where a quadrant would leave
+// the waves unequal work, with the same MFMA sequence per element (so the same bits):
+//   gemm_syrk_128  the diagonal tiles' updates, lower 16-blocks only, nine per wave
+//   gemm_deal_128  the inverse levels' products, whose K range holds one triangular 128-deep block:
+//                  wave w owns blocks w and 7 - w of the triangular dimension, the dense chunks run
+//                  without a predicate and the triangular block's eight chunks are unrolled
 #pragma once
 #include "mk_common.hpp"
 
@@ -469,6 +476,165 @@ __device__ inline void store_tile_syrk_lds(double* T, int tld, const AccSyrk& ac
   for (int rb = 0; rb < 8; ++rb)
 #pragma unroll
     for (int cb = rb + 1; cb < 8; ++cb) T[(16 * rb + zr) + (16 * cb + zc) * tld] = 0.0;
+}
+
+// ---------------------------------------------------------------- dealt body: one triangular 128-deep K block
+// acc += (NEG ? -1 : 1) op(A)[128 x K] * op(B)[K x 128] (A m-contiguous, B k-contiguous, K a multiple
+// of 128) where one 128-deep K block is lower-triangular -- the inverse levels' products:
+//   row-dealt    (!COL): op(A) lower in (m, k) over the LAST K block, ascending chunks: chunk c' of
+//                        that block only touches row blocks >= c'          (gemm_tile's SKIP_TRI_A)
+//   column-dealt (COL):  op(B) lower in (k, n) over the FIRST K block, which the descending order
+//                        reaches last: chunk c' only touches column blocks <= c'     (SKIP_TRI_BL)
+// A skip inside the quadrant body is unbalanced (the waves that own blocks 0-3 of the triangular
+// dimension keep 26 of their 32 (block, chunk) pairs, the others 10: the tile costs 26/32 of a dense
+// one) and puts a predicate before every MFMA of every chunk.  Here wave w owns the two 16-blocks
+// w and 7 - w along the triangular dimension and all eight along the other (2 + 8 fragments and 16
+// MFMAs per k-step), so every wave keeps 9 of its 16 (block, chunk) pairs, and the K loop is split:
+// the dense chunks run with no predicate, the triangular block's eight chunks are unrolled with c'
+// a compile-time constant.  For a given c' at most one of a wave's two blocks depends on w: one
+// wave-uniform branch around a group of 8 MFMAs per k-step.
+// Per element the MFMA sequence is mma_chunk's (the same chunks in the same order, four k-steps
+// with k = 4 ks + (lane >> 4), first operand the B fragment, second the A fragment) and the skipped
+// set is SKIP_TRI_A's / SKIP_TRI_BL's, so every element has the bits gemm_tile gives it.
+// Accumulator (d: the dealt block, 0 -> w, 1 -> 7 - w; o: the block along the other dimension):
+//   row-dealt    v[d][o]: C[16 blk(d) + (l & 15)][16 o + (l >> 4) + 4r]
+//   column-dealt v[o][d]: C[16 o + (l & 15)][16 blk(d) + (l >> 4) + 4r]
+template <bool COL>
+using AccDeal = AccT<COL ? 8 : 2, COL ? 2 : 8>;
+__host__ __device__ constexpr int deal_blk(int w, int d) { return d == 0 ? w : 7 - w; }
+// is block blk of the triangular dimension touched by chunk cp of the triangular K block?
+__host__ __device__ constexpr bool deal_live(bool col, int blk, int cp) { return col ? blk <= cp : blk >= cp; }
+// the same for dealt block d of EVERY wave (d = 0: blocks 0..3, d = 1: blocks 4..7): these decide at
+// compile time; what is left is one wave-uniform test
+__host__ __device__ constexpr bool deal_always(bool col, int d, int cp) {
+  return deal_live(col, col ? 4 * d + 3 : 4 * d, cp);
+}
+__host__ __device__ constexpr bool deal_never(bool col, int d, int cp) {
+  return !deal_live(col, col ? 4 * d : 4 * d + 3, cp);
+}
+// every live (block, chunk) exactly once and nothing else, 9 of 16 per wave, the compile-time
+// classes agree with deal_live on every wave, and at most one block per chunk is left to a branch
+constexpr bool deal_cover_exact(bool col) {
+  int cnt[8][8] = {};
+  for (int w = 0; w < 4; ++w) {
+    int mine = 0;
+    for (int cp = 0; cp < 8; ++cp) {
+      int branches = 0;
+      for (int d = 0; d < 2; ++d) {
+        const int blk = deal_blk(w, d);
+        const bool live = deal_live(col, blk, cp);
+        if (deal_always(col, d, cp) && !live) return false;
+        if (deal_never(col, d, cp) && live) return false;
+        if (deal_always(col, d, cp) && deal_never(col, d, cp)) return false;
+        if (!deal_always(col, d, cp) && !deal_never(col, d, cp)) ++branches;
+        if (live) {
+          ++cnt[blk][cp];
+          ++mine;
+        }
+      }
+      if (branches > 1) return false;
+    }
+    if (mine != 9) return false;
+  }
+  for (int blk = 0; blk < 8; ++blk)
+    for (int cp = 0; cp < 8; ++cp)
+      if (cnt[blk][cp] != (deal_live(col, blk, cp) ? 1 : 0)) return false;
+  return true;
+}
+static_assert(deal_cover_exact(false) && deal_cover_exact(true),
+              "both deals cover the live (block, chunk) pairs exactly once, nine per wave");
+
+// Element coordinates of accumulator (bm, bn, r) for this lane (within the 128 x 128 tile).
+template <bool COL>
+__device__ inline int deal_row(int w, int bm) { return 16 * (COL ? bm : deal_blk(w, bm)) + (threadIdx.x & 15); }
+template <bool COL>
+__device__ inline int deal_col(int w, int bn, int r) {
+  return 16 * (COL ? deal_blk(w, bn) : bn) + ((threadIdx.x & 63) >> 4) + 4 * r;
+}
+
+// CP: the chunk's index c' inside the triangular K block, -1 for a dense chunk.
+template <bool COL, bool NEG, int CP>
+__device__ inline void mma_chunk_deal(const double* As, const double* Bs, AccDeal<COL>& acc, int w) {
+  constexpr int BM = COL ? 8 : 2, BN = COL ? 2 : 8;
+  const int lane = threadIdx.x & 63;
+  const int li = lane & 15, lk = lane >> 4;
+#pragma unroll
+  for (int ks = 0; ks < GB_K / 4; ++ks) {
+    const int k = ks * 4 + lk;
+    double ya[BM], xb[BN];
+#pragma unroll
+    for (int b = 0; b < BM; ++b) {
+      const double av = frag<true, 128>(As, 16 * (COL ? b : deal_blk(w, b)) + li, k);
+      ya[b] = NEG ? -av : av;
+    }
+#pragma unroll
+    for (int b = 0; b < BN; ++b) xb[b] = frag<false, 128>(Bs, 16 * (COL ? deal_blk(w, b) : b) + li, k);
+#pragma unroll
+    for (int d = 0; d < 2; ++d) {
+      if (CP >= 0 && deal_never(COL, d, CP)) continue;
+      if (CP >= 0 && !deal_always(COL, d, CP) && !deal_live(COL, deal_blk(w, d), CP)) continue;   // wave-uniform
+#pragma unroll
+      for (int o = 0; o < 8; ++o) {
+        if constexpr (COL)
+          acc.v[o][d] = __builtin_amdgcn_mfma_f64_16x16x4f64(xb[d], ya[o], acc.v[o][d], 0, 0, 0);
+        else
+          acc.v[d][o] = __builtin_amdgcn_mfma_f64_16x16x4f64(xb[o], ya[d], acc.v[d][o], 0, 0, 0);
+      }
+    }
+  }
+}
+
+// K >= 128, K % 128 == 0: K / 16 - 8 dense chunks, then the triangular block's eight (none dense
+// when the triangular block is the whole K range).  REV as in gemm_tile; the column deal's
+// triangular block is the first, so COL goes with REV and !COL with ascending chunks.
+// lds: gb_lds_bytes(128, 128).  Ends with a barrier (the caller may reuse the LDS).
+template <bool COL, bool NEG>
+__device__ inline void gemm_deal_128(const double* __restrict__ A, long sA, const double* __restrict__ B, long sB, int K,
+                                     AccDeal<COL>& acc, double* lds) {
+  constexpr bool REV = COL;
+  constexpr int IMG = gb_img(128), STAGE = 2 * IMG;
+  const int nch = K / GB_K, nd = nch - 128 / GB_K;   // nd is even: a chunk's stage is its parity in either part
+  const int w = syrk_wave();
+  auto k_of = [&](int c) { return REV ? K - GB_K * (c + 1) : GB_K * c; };
+  auto issue = [&](int c) {
+    double* st = lds + (c & 1) * STAGE;
+    dma_chunk<true, 128>(A, sA, k_of(c), st);
+    dma_chunk<false, 128>(B, sB, k_of(c), st + IMG);
+  };
+  issue(0);
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  for (int c = 0; c < nd; ++c) {
+    const double* st = lds + (c & 1) * STAGE;
+    // the stage chunk c+1 overwrites was last read in iteration c-1, which every wave has left
+    issue(c + 1);
+    mma_chunk_deal<COL, NEG, -1>(st, st + IMG, acc, w);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+  }
+#define MK_DEAL_TRI(t)                                                              \
+  {                                                                                 \
+    const double* st = lds + ((t) & 1) * STAGE;                                     \
+    if ((t) < 7) issue(nd + (t) + 1);                                               \
+    mma_chunk_deal<COL, NEG, REV ? 7 - (t) : (t)>(st, st + IMG, acc, w);            \
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                                \
+    __syncthreads();                                                                \
+  }
+  MK_DEAL_TRI(0) MK_DEAL_TRI(1) MK_DEAL_TRI(2) MK_DEAL_TRI(3)
+  MK_DEAL_TRI(4) MK_DEAL_TRI(5) MK_DEAL_TRI(6) MK_DEAL_TRI(7)
+#undef MK_DEAL_TRI
+}
+
+// C = acc (column-major, ldc): lanes walk 16 consecutive rows of a column, as in store_tile.
+template <bool COL>
+__device__ inline void store_tile_deal(double* C, long ldc, const AccDeal<COL>& acc) {
+  const int w = syrk_wave();
+#pragma unroll
+  for (int bm = 0; bm < (COL ? 8 : 2); ++bm)
+#pragma unroll
+    for (int bn = 0; bn < (COL ? 2 : 8); ++bn)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) C[deal_row<COL>(w, bm) + (long)deal_col<COL>(w, bn, r) * ldc] = acc.v[bm][bn][r];
 }
 
 }  // namespace mk

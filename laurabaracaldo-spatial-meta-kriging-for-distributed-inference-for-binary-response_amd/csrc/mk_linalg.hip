@@ -1029,7 +1029,8 @@ __global__ __launch_bounds__(256) void k_chol_diag(MatSet ms, const int* __restr
 // MK_TRI_SKIP (compile time, default 1): the inverse levels skip the MFMA blocks of their diagonal W
 // tiles' zero triangles (SKIP_TRI_A / SKIP_TRI_BL, mk_gemm.hpp: ~15 % of the top level's MFMAs);
 // measured 0.570 -> 0.581 of peak over the inverse (profiles/r06/tri_skip).  0 builds the dense form
-// (A/B builds only: the same results, the skipped products are exact zeros).
+// (A/B builds only: the same results, the skipped products are exact zeros).  It governs the quadrant
+// body (the sub-tile instances, and the 128-tile one under MK_INV_DEAL=0); the dealt body always skips.
 #ifndef MK_TRI_SKIP
 #define MK_TRI_SKIP 1
 #endif
@@ -1065,9 +1066,13 @@ __global__ __launch_bounds__(256) void k_inv_copydiag(MatSet ms, const int* __re
 //   phase 1: W_BT = -W_BB Y_BT
 // with W_TT, W_BB complete from the lower levels.  Triangularity bounds every K range.
 // TM = 64: each 128-tile on four workgroups (small shards), bit-identical.
+// deal (MK_INV_DEAL, mk_schedule.hip; TM = 128 only): both products in the dealt body (gemm_deal_128,
+// mk_gemm.hpp: column-dealt for phase 0, row-dealt for phase 1) instead of the quadrant body with its
+// per-MFMA predicates -- the same MFMA sequence per element and the same skipped blocks, so the same
+// bits; the sub-tile instances keep the quadrant body.
 template <int TM>
 __global__ __launch_bounds__(256, 2) void k_inv_level(MatSet ms, const int* __restrict__ list,
-                                                      const int* __restrict__ count, int sz, int phase) {
+                                                      const int* __restrict__ count, int sz, int phase, int deal) {
   extern __shared__ __attribute__((aligned(16))) double lds[];   // gb_lds_bytes(TM, TM)
   constexpr int SUBR = MK_NB / TM, SUB = SUBR * SUBR;
   const int npairs = (ms.nt + 2 * sz - 1) / (2 * sz);
@@ -1091,6 +1096,26 @@ __global__ __launch_bounds__(256, 2) void k_inv_level(MatSet ms, const int* __re
   double* Y = ms.Y ? ms.Y + (long)sh * mat_elems(ms) : mat_slot(ms, sh, 1 - cur);
   const int ro = sr * TM;             // sub-tile row / column offsets in the 128-tile
   const long co = (long)sc * TM * ld;
+  if constexpr (TM == 128) {
+    if (deal) {
+      // the same two products with the triangular K block's 16-blocks dealt evenly over the waves
+      if (phase == 0) {
+        const double* Lm = mat_slot(ms, sh, cur);
+        AccDeal<true> acc;
+        acc_zero(acc);
+        gemm_deal_128<true, false>(Lm + i * MK_NB + (long)j * MK_NB * ld, ld, Wm + j * MK_NB + (long)j * MK_NB * ld, ld,
+                                   (B0 - j) * MK_NB, acc, lds);
+        store_tile_deal<true>(Y + i * MK_NB + (long)j * MK_NB * ld, ld, acc);
+      } else {
+        AccDeal<false> acc;
+        acc_zero(acc);
+        gemm_deal_128<false, true>(Wm + i * MK_NB + (long)B0 * MK_NB * ld, ld, Y + B0 * MK_NB + (long)j * MK_NB * ld, ld,
+                                   (i - B0 + 1) * MK_NB, acc, lds);
+        store_tile_deal<false>(Wm + i * MK_NB + (long)j * MK_NB * ld, ld, acc);
+      }
+      return;
+    }
+  }
   AccT<TM / 32, TM / 32> acc;
   acc_zero(acc);
   if (phase == 0) {
@@ -1111,9 +1136,9 @@ __global__ __launch_bounds__(256, 2) void k_inv_level(MatSet ms, const int* __re
     store_tile(Wm + i * MK_NB + ro + (long)j * MK_NB * ld + co, ld, acc);
   }
 }
-template __global__ void k_inv_level<128>(MatSet, const int*, const int*, int, int);
-template __global__ void k_inv_level<64>(MatSet, const int*, const int*, int, int);
-template __global__ void k_inv_level<32>(MatSet, const int*, const int*, int, int);
+template __global__ void k_inv_level<128>(MatSet, const int*, const int*, int, int, int);
+template __global__ void k_inv_level<64>(MatSet, const int*, const int*, int, int, int);
+template __global__ void k_inv_level<32>(MatSet, const int*, const int*, int, int, int);
 
 // Tiles (i,j), i >= j, of R^-1 = sum over rows l < n_s of W(l,i)^T W(l,j) (drops the bordered
 // row and the padding).  diag_only: tiles (i,i) into QB; otherwise the full symmetric Q.

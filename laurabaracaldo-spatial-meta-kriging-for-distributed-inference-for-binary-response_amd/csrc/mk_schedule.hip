@@ -141,6 +141,15 @@ static int diag_syrk() {
   return on != 0;
 }
 
+// MK_INV_DEAL (default 1, read once per process): the 128-tile inverse levels deal the 16-blocks of
+// their triangular K block evenly over the waves and keep the predicates out of the dense chunks
+// (gemm_deal_128, mk_gemm.hpp); 0: the quadrant body with a predicate before every MFMA.  An argument
+// of the kernel, so one build serves both arms of an A/B; same bits.
+static int inv_deal() {
+  static const int on = env_int("MK_INV_DEAL", 1);
+  return on != 0;
+}
+
 static void chol_update(mk_session* s, Group& g, hipStream_t st, int h0, int hc, int k, int ia, int ib, int j0, int j1,
                         const int* slist, const int* scount, double flops) {
   const int E = g.S * hc, nti = ib - ia;
@@ -373,13 +382,13 @@ void mk::launch_trinv(mk_session* s, Group& g, int max_entries, const int* list,
       auto launch = [&] {
         if (tm == 32)
           MK_LAUNCH(k_inv_level<32>, dim3(xcd_grid_h(max_entries, npairs * sz * sz * 16)), dim3(256), LDS_32,
-                             g.stream, g.ms, list, count, sz, phase);
+                             g.stream, g.ms, list, count, sz, phase, inv_deal());
         else if (tm == 64)
           MK_LAUNCH(k_inv_level<64>, dim3(xcd_grid_h(max_entries, npairs * sz * sz * 4)), dim3(256), LDS_64,
-                             g.stream, g.ms, list, count, sz, phase);
+                             g.stream, g.ms, list, count, sz, phase, inv_deal());
         else
           MK_LAUNCH(k_inv_level<128>, dim3(xcd_grid_h(max_entries, npairs * sz * sz)), dim3(256), LDS_128,
-                             g.stream, g.ms, list, count, sz, phase);
+                             g.stream, g.ms, list, count, sz, phase, inv_deal());
       };
       if (cnt >= 0)
         timed(s, g.stream, KS_INV, per, launch, cnt);
