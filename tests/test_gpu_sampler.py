@@ -13,10 +13,11 @@ TOL = 1e-8
 
 
 def _run_both(mk, n, q, cov, n_test=12, n_batch=3, batch_length=4, burn_in=7, seed=9, subset_base=0, S=2,
-              sizes=None, link="logit", lookahead=None, chunks=None):
+              sizes=None, link="logit", lookahead=None, chunks=None, weight=1):
     sizes = list(sizes) if sizes is not None else [n] * S
     off = np.concatenate([[0], np.cumsum(sizes)])
-    d = mk.synthetic.generate(int(off[-1]), q=q, n_test=n_test, seed=seed + q, cov_model=cov, link=link)
+    d = mk.synthetic.generate(int(off[-1]), q=q, n_test=n_test, seed=seed + q, cov_model=cov, link=link,
+                              weight=weight)
     ct = d["coords_test"] if n_test else None
     p = 2 * q
     kw = dict(n_batch=n_batch, batch_length=batch_length, burn_in=burn_in, seed=seed)
@@ -28,7 +29,8 @@ def _run_both(mk, n, q, cov, n_test=12, n_batch=3, batch_length=4, burn_in=7, se
     for s, m in enumerate(sizes):
         sl = slice(off[s], off[s] + m)
         rows = slice(off[s] * q, (off[s] + m) * q)
-        subs.append(dict(coords=d["coords"][sl], y=d["y"][rows], weights=np.ones(m * q), x=d["x"][rows]))
+        subs.append(dict(coords=d["coords"][sl], y=d["y"][rows], weights=np.full(m * q, float(weight)),
+                         x=d["x"][rows]))
     with mk.Session(subs, cfg, coords_test=ct, subset_base=subset_base, record_w=True, lookahead=lookahead) as ses:
         if lookahead is not None:
             assert ses.lookahead == bool(lookahead)
@@ -124,6 +126,16 @@ def test_replay_probit_matches_oracle(mk, n, q, cov):
     """Probit link (north-star "logit/probit"; the reference is logit, so the oracle's probit
     likelihood is the spec): y log Phi(eta) + (wt - y) log Phi(-eta) in the beta and w steps."""
     dev, refs = _run_both(mk, n, q, cov, link="probit")
+    _check(dev, refs)
+
+
+@pytest.mark.parametrize("n,q,cov,link", [(150, 1, 0, "logit"), (129, 1, 0, "probit"), (64, 2, 0, "logit")])
+def test_replay_binomial_trials(mk, n, q, cov, link):
+    """Binomial counts out of 5 trials (the ABI, the R wrapper and loglik_term(y, wt, eta, link) take
+    counts and trials; every other replay has weights of 1): k_beta, the block sweeps (q = 2) and the
+    site sweep (q = 1; n = 129 puts the bordered row in a tile of its own) each read wt through
+    their own loads, with padding."""
+    dev, refs = _run_both(mk, n, q, cov, link=link, weight=5)
     _check(dev, refs)
 
 
