@@ -188,7 +188,9 @@ int mk_session_tile_grids_wp(mk_session* s, int32_t t0, double* out_w, double* o
  * = exact kriging-variance evaluations, total_ms = the largest per-tile check difference (not a time);
  * 13 tiles whose check failed and were replayed exactly -- launches, total_ms = the largest failing
  * difference; 14 the chain-diagnostic launches k_chain_diag / k_chain_diag_prob -- launches and ms,
- * timed whether or not profiling is on; 0 launches unless diagnostics were asked for).  Flops are algorithmic, not executed: GEMM tiles 2 m n k, the diagonal tile's
+ * timed whether or not profiling is on; 0 launches unless diagnostics were asked for; 15 the
+ * model-assessment launches k_crit_accum / k_crit_replay / k_crit_finish / k_crit_total -- launches and
+ * ms, always timed, 0 launches unless criteria were asked for).  Flops are algorithmic, not executed: GEMM tiles 2 m n k, the diagonal tile's
  * update as a SYRK, solves and inverse products over their triangles.  mk_session_profile(s, enable)
  * before mk_session_run: enable 0 = off, 1 = every kind, otherwise a mask with bit (1 + kind) per kind
  * bracketed (e.g. 2 << 0 = the panel update only; fewer events, less overhead). */
@@ -290,6 +292,55 @@ int mk_meta_fit_diag(const mk_problem* prob, const mk_config* cfg, const int32_t
  * column (a coda mcmc matrix such as p.beta.theta.samples; t(p.w.samples) for the latent draws);
  * out is 3 x n_cols column-major. */
 int mk_chain_diagnostics(const double* x, int32_t n_rows, int64_t n_cols, double* out, int32_t device);
+
+/* ---- model assessment: spDiag's deviance information criterion, and WAIC, per subset ----
+ * Per subset, over the window's states k = 1..n and its observations i (site x outcome, location-major,
+ * i < n_s q; padding rows are masked):
+ *   eta_ik = x_i' beta_k + w_ik, recomputed from X, beta_k and w_k: fused multiply-adds in column order
+ *            from zero, then + w (as the predictive probabilities build theirs; not the chain's running
+ *            eta, which carries the rounding of its incremental updates)
+ *   l_ik   = the chain's likelihood term with the binomial coefficient dropped:
+ *            logit y eta - wt log(1 + e^eta); probit y log Phi(eta) + (wt - y) log Phi(-eta)
+ *   D_k = -2 sum_i l_ik
+ *   bar.D       = (1/n) sum_k D_k
+ *   D.bar.Omega = -2 sum_i l(y_i, wt_i, x_i' beta_bar + w_bar_i), beta_bar and w_bar the window means
+ *   pD  = bar.D - D.bar.Omega
+ *   DIC = bar.D + pD
+ *   lppd   = sum_i [log sum_k exp(l_ik) - log n]   (streaming log-sum-exp: running maximum, scaled sum)
+ *   p.waic = sum_i M2_i / (n - 1), M2_i = sum_k (l_ik - mean_i)^2 by Welford's update
+ *   WAIC   = -2 (lppd - p.waic)
+ *   lconst = sum_i [lgamma(wt + 1) - lgamma(y + 1) - lgamma(wt - y + 1)]
+ * lconst is the constant the likelihood terms drop (0 for binary data): full-likelihood figures add
+ * -2 lconst to bar.D, D.bar.Omega, DIC and WAIC and + lconst to lppd; pD and p.waic do not change.
+ * The first four rows are spDiag's for the binomial family as spBayes names them (parity by
+ * definition: no spBayes run pins them).  n >= 2 states, else MK_E_ARG.  A likelihood term that is
+ * not finite makes the subset's first seven rows NaN (lconst depends on the data alone).  Every sum
+ * runs in an order fixed by n and n_pad q alone, and the in-chain and the replayed route perform the
+ * same operations in the same order per observation: their results are equal bit for bit. */
+#define MK_N_CRIT 8   /* rows: bar.D, D.bar.Omega, pD, DIC, lppd, p.waic, WAIC, lconst */
+typedef struct mk_criteria {   /* caller-allocated, any pointer may be NULL */
+  double* subsets;     /* [n_subsets] x 8                                                        */
+  double* total;       /* 8: sums over this call's subsets in subset order                       */
+  double* pointwise;   /* [n_subsets] concatenated (n_s q) x 2 column-major: lppd_i, M2_i/(n-1)  */
+} mk_criteria;
+/* In-chain accumulation: from the first kept iteration on, one elementwise launch per kept iteration
+ * carries the running sums (6 doubles per observation and one partial per 256 observations and kept
+ * state of HBM, allocated here and only here).  Before the first mk_session_run only; later is
+ * MK_E_ARG.  Sessions that will only replay do not need it. */
+int mk_session_set_criteria(mk_session* s, int32_t enable);
+/* After all iterations.  With no kept window set, thin = 1 and in-chain accumulation on: closes the
+ * in-chain sums (window burn_in .. n.samples).  Otherwise replays states first, first + thin, ... <=
+ * last of the window (mk_session_set_kept_window, else burn_in .. n.samples) from the recorded chain:
+ * that needs record_samples and record_w, else MK_E_ARG.  For this call mk_session_set_kept_window
+ * also serves sessions without predict_tile that recorded both (their outputs are not windowed). */
+int mk_session_criteria(mk_session* s, int32_t thin, mk_criteria* out);
+/* mk_meta_fit_diag with the criteria of all K subsets (mk_meta_fit and mk_meta_fit_diag are this call
+ * with NULLs): every device block accumulates in chain and fills its subsets' rows (and pointwise
+ * pairs) at their global offsets; total is the sum of the K rows in global subset order, formed by
+ * the calling thread -- the order one session uses, so equal to it bit for bit. */
+int mk_meta_fit_ex(const mk_problem* prob, const mk_config* cfg, const int32_t* devices, int32_t n_devices,
+                   mk_progress_fn progress, void* user, mk_outputs* out, mk_combined* comb, mk_diagnostics* diag,
+                   mk_criteria* crit);
 
 /* ---- combine (MK.R:123-133): out = (grid_1 + ... + grid_K) / K, sequential order ---- */
 int mk_combine(const double* grids, int32_t K, int64_t grid_len, double* out, int32_t device);

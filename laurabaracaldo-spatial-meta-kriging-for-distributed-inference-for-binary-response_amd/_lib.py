@@ -25,6 +25,8 @@ MK_LINK_LOGIT = 0
 MK_LINK_PROBIT = 1
 N_LEVELS = 200
 N_DIAG = 3             # MK_N_DIAG: rows ess, mcse, rhat
+N_CRIT = 8             # MK_N_CRIT: the rows of mk_criteria, in CRIT_NAMES' order
+CRIT_NAMES = ["bar.D", "D.bar.Omega", "pD", "DIC", "lppd", "p.waic", "WAIC", "lconst"]
 
 _dp = ctypes.POINTER(ctypes.c_double)
 _ip = ctypes.POINTER(ctypes.c_int32)
@@ -77,10 +79,19 @@ class Diagnostics(ctypes.Structure):
                 ("w_predict_worst", _dp), ("p_predict_worst", _dp)]
 
 
+class Criteria(ctypes.Structure):
+    _fields_ = [("subsets", _dp), ("total", _dp), ("pointwise", _dp)]
+
+
 # int (*mk_progress_fn)(void* user, int32_t iterations, int32_t n_samples)
 PROGRESS_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32)
 
 EXPORTS = {
+    "mk_meta_fit_ex": (ctypes.c_int, [ctypes.POINTER(Problem), ctypes.POINTER(Config), _ip, ctypes.c_int32,
+                                      PROGRESS_FN, ctypes.c_void_p, ctypes.POINTER(Outputs), ctypes.POINTER(Combined),
+                                      ctypes.POINTER(Diagnostics), ctypes.POINTER(Criteria)]),
+    "mk_session_set_criteria": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32]),
+    "mk_session_criteria": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(Criteria)]),
     "mk_meta_fit": (ctypes.c_int, [ctypes.POINTER(Problem), ctypes.POINTER(Config), _ip, ctypes.c_int32,
                                    PROGRESS_FN, ctypes.c_void_p, ctypes.POINTER(Outputs), ctypes.POINTER(Combined)]),
     "mk_meta_fit_diag": (ctypes.c_int, [ctypes.POINTER(Problem), ctypes.POINTER(Config), _ip, ctypes.c_int32,

@@ -156,6 +156,7 @@ mk_session::~mk_session() {
   if (device >= 0) hipSetDevice(device);
   for (auto& o : owned) hipStreamSynchronize(o.second);
   for (auto& t : prof.pending) { hipEventDestroy(t.a); hipEventDestroy(t.b); }
+  for (auto& t : crit.pending) { hipEventDestroy(t.a); hipEventDestroy(t.b); }
   if (prof.inv_cnt) hipHostFree(prof.inv_cnt);
   for (auto& g : groups) {
     if (g.done) hipEventDestroy(g.done);
@@ -790,6 +791,7 @@ extern "C" int mk_session_run(mk_session* s, int32_t n_iter) {
     for (hipStream_t st : {s->la.m, s->la.c, s->la.k, s->cov.st}) if (st) (void)hipStreamSynchronize(st);
     s->kt.pending = false;
     for (auto& g : s->groups) (void)hipStreamSynchronize(g.stream);
+    crit_drain(s, false);
     return set_err(MK_E_HIP, std::string("kernel launch in iteration ") + std::to_string(s->iter - 1) + ": " +
                                  hipGetErrorString(le));
   }
@@ -801,6 +803,7 @@ extern "C" int mk_session_run(mk_session* s, int32_t n_iter) {
     HIPCHK(hipEventSynchronize(s->kt.ev[1]));
     s->kt.pending = false;
   }
+  crit_drain(s, true);
   if (s->sweep.coop) {
     // the multi-workgroup sweep's barrier time-out (after admission every wait completes: this is the
     // net under that argument): its chain state is then not the sampler's -- the session is

@@ -125,6 +125,11 @@ __global__ void k_pred_tab_draw(Model md, ChebK c, const double* g, const double
                                 const double* As, int iter, int kidx);
 __global__ void k_pred_cheb_draw(Model md, ChebK c, const double* Gt, const double* phit, const double* coords,
                                  const double* kA, int k_lo, int nkp);
+// mk_criteria.hip
+__global__ void k_crit_accum(Model md, Crit c, int kidx);
+__global__ void k_crit_replay(Model md, Crit c, int first, int n, int thin);
+__global__ void k_crit_finish(Model md, Crit c, int n, double* rows, double* pointwise);
+__global__ void k_crit_total(const double* rows, int S, double* out);
 // mk_post.hip
 __global__ void k_weiszfeld(const double* grids, int K, int L, long C, int max_iter, double tol, double* out, int* iters);
 __global__ void k_post_index(uint64_t seed, int samplesize, int n_levels, int* idx);

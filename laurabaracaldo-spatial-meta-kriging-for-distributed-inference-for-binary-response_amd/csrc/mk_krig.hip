@@ -167,10 +167,17 @@ int mk::pred_prob_to_host(mk_session* s, int subset, int t0, int n_rows, int n_c
 
 extern "C" int mk_session_set_kept_window(mk_session* s, int32_t first, int32_t last) {
   if (!s) return set_err(MK_E_ARG, "null session");
-  if (!s->tiled) return set_err(MK_E_ARG, "kept windows need a session created with predict_tile > 0");
   const int lo = s->md.kept0 + 1, hi = s->md.n_samples;
+  // a session that is not tiled but recorded samples and w: the window serves mk_session_criteria alone
+  const bool crit_only = !s->tiled && s->md.samples && s->md.w_samples;
+  if (!s->tiled && !crit_only) return set_err(MK_E_ARG, "kept windows need a session created with predict_tile > 0");
   if (first < lo || last < first || last > hi)
     return set_err(MK_E_ARG, "kept window must satisfy burn_in <= first <= last <= n.samples");
+  if (crit_only) {
+    s->crit.win_lo = first - lo;
+    s->crit.win_n = last - first + 1;
+    return 0;
+  }
   s->win_lo = first - lo;
   s->win_n = last - first + 1;
   return 0;

@@ -391,12 +391,18 @@ void fold_worst(double* into, const double* blk, long n, bool first) {
 
 extern "C" int mk_meta_fit(const mk_problem* pr, const mk_config* c, const int32_t* devices, int32_t G,
                            mk_progress_fn progress, void* user, mk_outputs* out, mk_combined* comb) {
-  return mk_meta_fit_diag(pr, c, devices, G, progress, user, out, comb, nullptr);
+  return mk_meta_fit_ex(pr, c, devices, G, progress, user, out, comb, nullptr, nullptr);
 }
 
 extern "C" int mk_meta_fit_diag(const mk_problem* pr, const mk_config* c, const int32_t* devices, int32_t G,
                                 mk_progress_fn progress, void* user, mk_outputs* out, mk_combined* comb,
                                 mk_diagnostics* diag) {
+  return mk_meta_fit_ex(pr, c, devices, G, progress, user, out, comb, diag, nullptr);
+}
+
+extern "C" int mk_meta_fit_ex(const mk_problem* pr, const mk_config* c, const int32_t* devices, int32_t G,
+                              mk_progress_fn progress, void* user, mk_outputs* out, mk_combined* comb,
+                              mk_diagnostics* diag, mk_criteria* crit) {
   if (!pr || !c) return fail(MK_E_ARG, "null problem/config");
   if (!devices || G < 1) return fail(MK_E_ARG, "n_devices must be >= 1 with a device list");
   const int K = pr->n_subsets;
@@ -418,6 +424,7 @@ extern "C" int mk_meta_fit_diag(const mk_problem* pr, const mk_config* c, const 
   const bool dg_w = diag && (diag->w_predict || diag->w_predict_worst);
   const bool dg_p = diag && (diag->p_predict || diag->p_predict_worst);
   if (dg_p && !pr->x_test) return fail(MK_E_ARG, "p_predict diagnostics need x_test");
+  const bool want_crit = crit && (crit->subsets || crit->total || crit->pointwise);
   const int q = pr->q, p = pr->p, n_samples = c->n_batch * c->batch_length;
   if (c->n_batch < 1 || c->batch_length < 1) return fail(MK_E_ARG, "n.batch and batch.length must be >= 1");
 
@@ -460,7 +467,8 @@ extern "C" int mk_meta_fit_diag(const mk_problem* pr, const mk_config* c, const 
     sp.x = pr->x + s0 * q * p;
     mk_config sc = *c;
     sc.device = x.dev;
-    return mk_session_create(&sp, &sc, &x.ses);
+    const int e = mk_session_create(&sp, &sc, &x.ses);
+    return (e || !want_crit) ? e : mk_session_set_criteria(x.ses, 1);
   });
   if (rc) return rc;
   if (nd.use_rccl) {
@@ -568,6 +576,29 @@ extern "C" int mk_meta_fit_diag(const mk_problem* pr, const mk_config* c, const 
       return mk_session_diagnostics(x.ses, &d);
     });
     if (rc) return rc;
+  }
+
+  // ---- model assessment (optional): every block closes its in-chain sums into its subsets' rows (and
+  // pointwise pairs) at their global offsets; the calling thread adds the K rows in global subset order,
+  // as k_crit_total does for one session
+  if (want_crit) {
+    std::vector<double> rows((size_t)K * MK_N_CRIT, 0.0);
+    rc = nd.pool->run([&](int r) -> int {
+      Block& x = *nd.b[r];
+      if (!x.ses) return 0;
+      mk_criteria cr{};
+      cr.subsets = rows.data() + (size_t)x.lo * MK_N_CRIT;
+      if (crit->pointwise) cr.pointwise = crit->pointwise + (size_t)site0[x.lo] * q * 2;
+      return mk_session_criteria(x.ses, 1, &cr);
+    });
+    if (rc) return rc;
+    if (crit->subsets) std::memcpy(crit->subsets, rows.data(), rows.size() * sizeof(double));
+    if (crit->total)
+      for (int e = 0; e < MK_N_CRIT; ++e) {
+        double acc = rows[e];
+        for (int i = 1; i < K; ++i) acc = acc + rows[(size_t)i * MK_N_CRIT + e];
+        crit->total[e] = acc;
+      }
   }
 
   // ---- the grids.  A whole grid kind ([S_r][Ck][200] per block, in x.grids): each block's grids to its subsets'

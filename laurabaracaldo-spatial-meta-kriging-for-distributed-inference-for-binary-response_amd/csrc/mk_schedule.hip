@@ -574,6 +574,7 @@ static void iteration_post_sweep(mk_session* s, Group& g, int it) {
   hipStream_t st = g.stream;
   if (s->record_samples) MK_LAUNCH(k_record, dim3((S + 63) / 64), dim3(64), 0, st, md, it);
   if (s->record_w) MK_LAUNCH(k_record_w, dim3((md.Np + 255) / 256, S), dim3(256), 0, st, md, it);
+  if (kept && s->crit.on) launch_crit_accum(s, g, it - md.kept0);
   if (kept && md.n_test > 0 && !s->tiled && s->kt.on) {
     // from the phi tables (krig_tables): z, phi and A captured now, then g = W' z and the draws on a
     // side stream -- the lookahead schedule's kriging stream, else the early assembly's stream after its

@@ -7,6 +7,7 @@
 //   mk_summary.hip   stateless entry points (combine, Weiszfeld, posterior summary, glm): no session
 //   mk_parity.hip    parity-test entry points
 //   mk_diag.hip      chain diagnostics: the launcher, the session entry points, the tile sink
+//   mk_criteria.hip  model assessment (DIC, WAIC): the kernels, the scratch, the session entry points
 //
 // mk_internal.hpp stays the interface towards mk_multi.hip and mk_watch.hip.
 #pragma once
@@ -47,7 +48,7 @@ static inline int env_int(const char* name, int dflt) {
   return (v && *v) ? std::atoi(v) : dflt;
 }
 
-constexpr int NKSTAT = 15;
+constexpr int NKSTAT = 16;
 // KS_CHOL_UPDATE: the 128-tile panel-update launches (k_chol_update<128>); KS_CHOL_UPDATE_SUB:
 // the 64- / 32-sub-tile ones (small grids).  Together: the roofline kernel k_chol_update.
 // KS_UPDATE_BUSY: both, with the time of launches that overlap (the split schedule's bulk and
@@ -56,13 +57,16 @@ constexpr int NKSTAT = 15;
 // bound: only the pairs whose factor changed are in the list -- bench_kriging counts exactly).
 // KS_COV: the candidates' covariance assembly (k_cov_candidate, with k_matern_table for Matern).
 enum { KS_CHOL_UPDATE = 0, KS_CHOL_DIAG, KS_CHOL_TRSM, KS_SWEEP, KS_LAUUM, KS_ITER, KS_INV, KS_CHOL_UPDATE_SUB,
-       KS_UPDATE_BUSY, KS_PRED_VAR, KS_COV, KS_SWEEP_FALLBACK, KS_KRIG_CHEB, KS_KRIG_FALLBACK, KS_DIAG };
+       KS_UPDATE_BUSY, KS_PRED_VAR, KS_COV, KS_SWEEP_FALLBACK, KS_KRIG_CHEB, KS_KRIG_FALLBACK, KS_DIAG, KS_CRIT };
 // KS_KRIG_CHEB: tiles kriged by phi interpolation (predict_tile_cheb): launches = tiles, flops = exact
 // s evaluations ((subset, node or check point) pairs), total_ms = the largest check difference seen
 // (not a time).  KS_KRIG_FALLBACK: tiles whose check failed and were replayed exactly (launches), and
 // total_ms the largest failing difference.
 // KS_DIAG: the chain-diagnostic launches (k_chain_diag, k_chain_diag_prob), bracketed by events whether
 // or not the profiler is on (a handful per call, each followed by a wait anyway).
+// KS_CRIT: the model-assessment launches (k_crit_accum per kept iteration and stream group, k_crit_replay,
+// k_crit_finish and k_crit_total per mk_session_criteria), bracketed by events whether or not the profiler
+// is on; none are made unless criteria were asked for.
 // KS_SWEEP_FALLBACK: launches = (subset, iteration) sweeps k_sweep_mg refused admission and its
 // k_sweep fallback ran (counted on the device, read at the end of every mk_session_run; no timing).
 
@@ -210,6 +214,17 @@ struct Profiler {
   Stat stats[NKSTAT];
 };
 
+// mk_criteria.hip.  In-chain model assessment (mk_session_set_criteria): the scratch the kept
+// iterations accumulate into (allocated when switched on, never otherwise), the events around their
+// launches (priced at the end of every mk_session_run), and the kept window of a session that is not
+// tiled (mk_session_set_kept_window; a tiled session's is win_lo / win_n).
+struct Criteria {
+  bool on = false;
+  Crit buf{};
+  std::vector<Timed> pending;
+  int win_lo = 0, win_n = -1;
+};
+
 }  // namespace mk
 
 struct mk_session {
@@ -246,6 +261,7 @@ struct mk_session {
   mk::ChebWindow cg;
   mk::SweepPlan sweep;
   mk::Profiler prof;
+  mk::Criteria crit;
   mk_diagnostics diag_sink{};           // mk_session_set_diagnostics: filled by every tile replay while diag_on
   bool diag_on = false;
   hipError_t launch_err = hipSuccess;   // first failed kernel launch of a run
@@ -362,5 +378,11 @@ int diag_to_host(mk_session* s, const double* data, long subset_stride, long row
                  const ProbSrc* ps, long col0, long C, double* h_each, double* h_worst);
 // The attached sink's share of tile [t0, ..): the draws are in md.w_pred ([S][n_kept][Ct]).
 int tile_diagnostics(mk_session* s, int t0, int n_kept, int Ct);
+
+// ---- mk_criteria.hip
+// Kept iteration kidx of group g (criteria on): k_crit_accum on the group's stream between two events.
+void launch_crit_accum(mk_session* s, Group& g, int kidx);
+// The events of the launches above: priced into KS_CRIT (price = false: only destroyed).  The streams are idle.
+void crit_drain(mk_session* s, bool price);
 
 }  // namespace mk

@@ -135,6 +135,21 @@ struct ProbSrc {
   int p, link;
 };
 
+// Model-assessment scratch (mk_criteria.hip; include/mk.h "model assessment").  Per observation
+// (subset s, row i of its Np) six running values over the window's states, plane a of subset s at
+// acc + (s * MK_CRIT_ACC + a) * Np: 0 the Welford mean of the log-likelihood terms, 1 their M2, 2 the
+// running maximum and 3 the scaled sum of the streaming log-sum-exp, 4 a flag (1 once a term was not
+// finite), 5 the sum of w.  part: the workgroups' sums of the terms, one per (subset, state, block of
+// 256 observations).  sbeta: the sum of beta.
+#define MK_CRIT_ACC 6
+struct Crit {
+  double* acc;     // [S][MK_CRIT_ACC][Np]
+  double* part;    // [S][n_cap][nb]
+  double* sbeta;   // [S][p]
+  int nb;          // ceil(Np / 256)
+  int n_cap;       // states the partials have room for
+};
+
 __device__ inline long mat_elems(const MatSet& m) { return (long)m.ld * m.ld; }
 __device__ inline double* mat_slot(const MatSet& m, int sh, int slot) {
   return m.L + ((long)sh * 2 + slot) * mat_elems(m);

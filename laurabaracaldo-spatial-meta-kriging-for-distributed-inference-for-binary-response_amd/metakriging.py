@@ -89,21 +89,26 @@ def r_sample_replace(n, size, seed):
 
 
 def meta_fit(y, x, weight, coords, q, index_part, coords_test=None, cfg=None, subset_base=0, device=0,
-             cov_model="exponential", n_batch=100, batch_length=50, seed=20250114, x_test=None, diagnostics=False):
+             cov_model="exponential", n_batch=100, batch_length=50, seed=20250114, x_test=None, diagnostics=False,
+             criteria=False):
     """All subsets of one shard on one GPU; returns the list `obj` of MK.R:108 for those subsets:
     [{'parameters': 200 x P, 'w.predict': 200 x (q n_test)}, ...]; with x_test (MK.R:87's x.test) each
     also holds 'p.predict' (200 x (q n_test)): the grid of p(y = 1) at the test sites.
     diagnostics=True: each also holds 'parameters.diagnostics' (3 x P: ess, mcse, split R-hat of its kept
-    chain) and, with test sites, 'w.predict.diagnostics' / 'p.predict.diagnostics' (3 x (q n_test))."""
+    chain) and, with test sites, 'w.predict.diagnostics' / 'p.predict.diagnostics' (3 x (q n_test)).
+    criteria=True: each also holds 'criteria', the subset's DIC and WAIC rows by name (bar.D, D.bar.Omega,
+    pD, DIC, lppd, p.waic, WAIC, lconst; Session.criteria), accumulated in chain over its kept states."""
     p = np.asarray(x).shape[1]
     if cfg is None:
         beta0, bt = start_values(y, x, weight, q)
         cfg = default_config(q, p, beta0, bt, cov_model=cov_model, n_batch=n_batch, batch_length=batch_length,
                              seed=seed)
     subsets = [subset_data(y, x, weight, coords, q, idx) for idx in index_part]
-    with Session(subsets, cfg, coords_test=coords_test, subset_base=subset_base, device=device, x_test=x_test) as ses:
+    with Session(subsets, cfg, coords_test=coords_test, subset_base=subset_base, device=device, x_test=x_test,
+                 criteria=criteria) as ses:
         ses.run(cfg.n_samples)
         out = ses.outputs(diagnostics=diagnostics)
+        crit = ses.criteria() if criteria else None
     res = []
     for i in range(len(subsets)):
         d = {"parameters": out["parameters"][i]}
@@ -114,6 +119,8 @@ def meta_fit(y, x, weight, coords, q, index_part, coords_test=None, cfg=None, su
         for kind in ("parameters", "w_predict", "p_predict"):
             if kind + "_diag" in out:
                 d[kind.replace("_", ".") + ".diagnostics"] = out[kind + "_diag"][i]
+        if crit is not None:
+            d["criteria"] = dict(zip(crit["names"], crit["subsets"][i].tolist()))
         res.append(d)
     return res
 
@@ -202,7 +209,7 @@ def posterior_summary(result, result2, x_test, q=None, samplesize=1000, seed=202
 
 def reference_flow(d, K, q, cov_model="exponential", n_batch=100, batch_length=50, seed=20250114, devices=(0,),
                    method="mean", predict_tile=0, partition_method="R", samplesize=1000, progress=None,
-                   predictive=False, diagnostics=False):
+                   predictive=False, diagnostics=False, criteria=False):
     """The reference script end to end in one process over the GPUs in `devices` (mk_meta_fit: the
     subsets sharded over them in-library, the combine device to device):
 
@@ -218,6 +225,8 @@ def reference_flow(d, K, q, cov_model="exponential", n_batch=100, batch_length=5
     subset's grids of p(y = 1) at the test sites are made and combined too, summary["result3"].
     diagnostics=True: the worst-over-subsets chain diagnostics come back as summary["diagnostics"]
     (the '*_diag_worst' arrays of meta_fit_node; convergence_report reads them).
+    criteria=True: the DIC and WAIC rows summed over the K subsets come back by name as
+    summary["criteria"] (meta_fit_node's 'criteria' total).
     Returns (phases, result, result2, summary, cfg) -- phases in seconds of
     wall clock: set-up (partition, glm, subset slicing), the chains (to the last batch boundary),
     quantiles + combine, post-processing, and the whole."""
@@ -243,7 +252,7 @@ def reference_flow(d, K, q, cov_model="exponential", n_batch=100, batch_length=5
 
     fit = meta_fit_node(subs, cfg, coords_test=d["coords_test"], devices=devices, method=method, per_subset=False,
                         progress=_progress, x_test=d["x_test"] if predictive else None,
-                        diagnostics=diagnostics)                                            # MK.R:100-133
+                        diagnostics=diagnostics, criteria=criteria)                         # MK.R:100-133
     t3 = time.perf_counter()
     t["chains_s"] = stamp.get("chains", t3) - t1
     t["quantiles_combine_s"] = t3 - stamp.get("chains", t3)
@@ -255,6 +264,8 @@ def reference_flow(d, K, q, cov_model="exponential", n_batch=100, batch_length=5
         summ["result3"] = fit["result3"]
     if diagnostics:
         summ["diagnostics"] = {k: v for k, v in fit.items() if k.endswith("_diag_worst")}
+    if criteria:
+        summ["criteria"] = dict(zip(fit["criteria"]["names"], fit["criteria"]["total"].tolist()))
     t["end_to_end_s"] = time.perf_counter() - t0
     t["exchange"] = fit["exchange"]          # the combine's all-to-all: "rccl" (distinct GPUs) or "copy"
     t["comm_ranks"] = fit["comm_ranks"]      # ranks RCCL's communicators hold (copies: device blocks)

@@ -15,7 +15,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import Combined, check
-from .outbuf import DiagnosticBuffers, OutputBuffers
+from .outbuf import CriteriaBuffers, DiagnosticBuffers, OutputBuffers
 from .session import PackedProblem
 
 N_LEVELS = _lib.N_LEVELS
@@ -24,7 +24,7 @@ N_LEVELS = _lib.N_LEVELS
 def meta_fit_node(subsets, cfg, coords_test=None, devices=(0,), subset_base=0, method="mean", per_subset=True,
                   samples=False, w_samples=False, w_pred_samples=False, acceptance=False, w_predict_sum=False,
                   progress=None, record_w=False, max_iter=100, tol=1e-12, x_test=None, p_pred_samples=False,
-                  p_predict_sum=False, diagnostics=False):
+                  p_predict_sum=False, diagnostics=False, criteria=False):
     """Fit all subsets over `devices` and combine.  Returns a dict with 'result' (200 x P, MK.R:127),
     'result2' (200 x q n_test, MK.R:133; None without test sites), 'exchange' ('rccl' / 'copy'),
     'comm_ranks' (the ranks the exchange spans: RCCL's own ncclCommCount, or the blocks for copies),
@@ -35,7 +35,10 @@ def meta_fit_node(subsets, cfg, coords_test=None, devices=(0,), subset_base=0, m
     linkinv(x.test beta + w) combined as result2 is), per subset 'p_predict', and the optional
     'p_pred_samples' / 'p_predict_sum'.  diagnostics=True (mk_meta_fit_diag) adds, as Session.outputs
     does, the chain diagnostics of all K subsets -- 'parameters_diag', 'w_predict_diag', 'p_predict_diag'
-    (per subset 3 x C: ess, mcse, split R-hat) -- and the '*_diag_worst' arrays (3 x C) over all K."""
+    (per subset 3 x C: ess, mcse, split R-hat) -- and the '*_diag_worst' arrays (3 x C) over all K.
+    criteria=True (mk_meta_fit_ex) adds 'criteria': Session.criteria's dict for all K subsets -- 'subsets'
+    (K x 8: bar.D, D.bar.Omega, pD, DIC, lppd, p.waic, WAIC, lconst), 'total' (their sums in global
+    subset order) and 'names'; criteria="pointwise" also the per-observation pairs."""
     lib = _lib.load()
     if method not in ("mean", "median"):
         raise ValueError(f"error: unknown combine method '{method}'")
@@ -73,8 +76,10 @@ def meta_fit_node(subsets, cfg, coords_test=None, devices=(0,), subset_base=0, m
     if diagnostics:
         kinds = ["parameters"] + (["w_predict"] if have else []) + (["p_predict"] if have_x else [])
         db = DiagnosticBuffers(K, cfg, n_test, {k + sfx for k in kinds for sfx in ("_diag", "_diag_worst")})
-    check(lib.mk_meta_fit_diag(ctypes.byref(pp.c), ctypes.byref(c), devs.ctypes.data_as(_lib._ip), len(devs), fn, None,
-                               ctypes.byref(ob.c), ctypes.byref(cb), ctypes.byref(db.c) if db is not None else None))
+    kb = CriteriaBuffers(K, q, pp.n_part, pointwise=criteria == "pointwise") if criteria else None
+    check(lib.mk_meta_fit_ex(ctypes.byref(pp.c), ctypes.byref(c), devs.ctypes.data_as(_lib._ip), len(devs), fn, None,
+                             ctypes.byref(ob.c), ctypes.byref(cb), ctypes.byref(db.c) if db is not None else None,
+                             ctypes.byref(kb.c) if kb is not None else None))
     del keep
     out = {"result": result.T.copy(), "result2": None if result2 is None else result2.T.copy(),
            "exchange": "rccl" if cb.exchange else "copy", "comm_ranks": int(cb.comm_ranks)}
@@ -83,4 +88,6 @@ def meta_fit_node(subsets, cfg, coords_test=None, devices=(0,), subset_base=0, m
     out.update(ob.unpack())
     if db is not None:
         out.update(db.unpack())
+    if kb is not None:
+        out["criteria"] = kb.unpack()
     return out

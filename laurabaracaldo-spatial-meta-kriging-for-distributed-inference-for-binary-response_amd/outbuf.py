@@ -2,7 +2,7 @@
 caller's layouts: one table of field -> shape serves Session.outputs and meta_fit_node."""
 import numpy as np
 
-from ._lib import N_DIAG, N_LEVELS, Diagnostics, Outputs, dptr
+from ._lib import CRIT_NAMES, N_CRIT, N_DIAG, N_LEVELS, Criteria, Diagnostics, Outputs, dptr
 
 # The array libmk fills for each mk_outputs field, row-major, in terms of: K subsets, P parameters,
 # C = q n_test kriging columns, L levels, n = n_samples, kept states, B amcmc batches, R = P + 1
@@ -90,3 +90,26 @@ class DiagnosticBuffers(OutputBuffers):
             if f in self.buf:
                 setattr(c, STRUCT_OF[f][1], dptr(self.buf[f]))
         return c
+
+
+class CriteriaBuffers:
+    """The arrays behind an mk_criteria of K subsets (n_part sites each, q outcomes): `.c` points at
+    them; unpack() gives {'subsets': (K, 8), 'total': (8,), 'names': the rows' names} and, with
+    pointwise, 'pointwise': per subset an (n_s q) x 2 array, columns lppd_i and M2_i / (n - 1)."""
+
+    def __init__(self, K, q, n_part, pointwise=False):
+        self.n_obs = [int(ns) * int(q) for ns in n_part]
+        self.subsets = np.zeros((int(K), N_CRIT))
+        self.total = np.zeros(N_CRIT)
+        self.pointwise = np.zeros(2 * sum(self.n_obs)) if pointwise else None
+        self.c = Criteria()
+        self.c.subsets, self.c.total, self.c.pointwise = dptr(self.subsets), dptr(self.total), dptr(self.pointwise)
+
+    def unpack(self):
+        out = {"subsets": self.subsets.copy(), "total": self.total.copy(), "names": list(CRIT_NAMES)}
+        if self.pointwise is not None:
+            out["pointwise"], off = [], 0
+            for N in self.n_obs:                              # column-major (n_s q) x 2 per subset
+                out["pointwise"].append(self.pointwise[off:off + 2 * N].reshape(2, N).T.copy())
+                off += 2 * N
+        return out

@@ -10,7 +10,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import Config, Problem, check, dptr, iptr
-from .outbuf import DiagnosticBuffers, OutputBuffers
+from .outbuf import CriteriaBuffers, DiagnosticBuffers, OutputBuffers
 
 COV_MODELS = {"exponential": _lib.MK_COV_EXPONENTIAL, "matern": _lib.MK_COV_MATERN}
 LINKS = {"logit": _lib.MK_LINK_LOGIT, "probit": _lib.MK_LINK_PROBIT}
@@ -19,6 +19,7 @@ LINKS = {"logit": _lib.MK_LINK_LOGIT, "probit": _lib.MK_LINK_PROBIT}
 (KS_CHOL_UPDATE, KS_CHOL_DIAG, KS_CHOL_TRSM, KS_SWEEP, KS_LAUUM, KS_ITER, KS_INV, KS_CHOL_UPDATE_SUB, KS_UPDATE_BUSY,
  KS_PRED_VAR, KS_COV, KS_SWEEP_FALLBACK, KS_KRIG_CHEB, KS_KRIG_FALLBACK) = range(14)
 KS_DIAG = 14      # the chain-diagnostic launches (always timed; 0 launches unless diagnostics were asked for)
+KS_CRIT = 15      # the model-assessment launches (always timed; 0 launches unless criteria were asked for)
 
 
 def _f64(a):
@@ -165,9 +166,10 @@ class Session:
 
     subsets: list of dicts with 'coords' (n_s,2), 'y' (n_s*q,), 'weights' (n_s*q,), 'x' (n_s*q, p).
     """
+    _fused = False
 
     def __init__(self, subsets, cfg, coords_test=None, subset_base=0, device=0, record_w=False, lookahead=None,
-                 x_test=None):
+                 x_test=None, criteria=False):
         self.cfg = cfg
         self.q, self.p = cfg.q, cfg.p
         self._prob = PackedProblem(subsets, cfg, coords_test, subset_base, x_test=x_test)
@@ -183,8 +185,17 @@ class Session:
         self._h = h
         self._lib = lib
         self._window = None     # kept states of the next outputs(), once set_kept_window narrowed them
-        if lookahead is not None:
-            self.set_lookahead(lookahead)
+        # kriging fused into the kept iterations (mk_session_create's rule): a kept window then serves
+        # criteria() alone, outputs() keeps every kept state
+        self._fused = not (cfg.predict_tile > 0 and (self.n_test == 0 or cfg.predict_tile < self.n_test))
+        try:
+            if lookahead is not None:
+                self.set_lookahead(lookahead)
+            if criteria:                # in-chain DIC / WAIC sums from the first kept iteration on
+                check(lib.mk_session_set_criteria(self._h, 1))
+        except Exception:
+            self.close()
+            raise
 
     def run(self, n_iter):
         check(self._lib.mk_session_run(self._h, int(n_iter)))
@@ -279,6 +290,19 @@ class Session:
         check(self._lib.mk_session_set_kept_window(self._h, int(first), int(last)))
         self._window = int(last) - int(first) + 1
 
+    def criteria(self, thin=1, pointwise=False):
+        """DIC and WAIC per subset after the run (mk_session_criteria; the definitions are in
+        include/mk.h): {'subsets': (S, 8), 'total': (8,) their sums in subset order, 'names': the rows
+        -- bar.D, D.bar.Omega, pD, DIC, lppd, p.waic, WAIC, lconst}; pointwise=True adds 'pointwise', per
+        subset (n_s q) x 2: lppd_i and the Welford variance term of p.waic.  A session made with
+        criteria=True closes its in-chain sums (kept states burn_in..n.samples); with a kept window
+        (set_kept_window), thin > 1 or no in-chain sums the recorded chain is replayed, which needs
+        record_w.  The likelihood drops the binomial coefficient: lconst is what full-likelihood
+        figures add (-2 lconst to the deviance rows and WAIC, + lconst to lppd)."""
+        cb = CriteriaBuffers(self.S, self.q, self.n_part, pointwise=pointwise)
+        check(self._lib.mk_session_criteria(self._h, int(thin), ctypes.byref(cb.c)))
+        return cb.unpack()
+
     def set_lookahead(self, mode):
         """Launch schedule before the first run: True / 1 lookahead (the next iteration's phi
         candidates factored while this iteration's inverse and sweep run), False / 0 sequential,
@@ -342,7 +366,7 @@ class Session:
                   w_samples=w_samples, w_pred_samples=w_pred_samples and have, acceptance=acceptance,
                   w_predict_sum=w_predict_sum and have, p_predict=p_predict, p_pred_samples=p_pred_samples,
                   p_predict_sum=p_predict_sum)
-        kept = self.cfg.kept if self._window is None else self._window
+        kept = self.cfg.kept if self._window is None or self._fused else self._window
         fields = {f for f, v in on.items() if v}
         if not diagnostics:
             ob = OutputBuffers(self.S, self.cfg, self.n_part, self.n_test, kept, fields)

@@ -144,6 +144,28 @@ def spDiagnostics(sp_obj, start=1, end=None):
     return ses.outputs(quantiles=False, diagnostics="parameters")["parameters_diag"][0]
 
 
+def spDiag(sp_obj, start=1, end=None, thin=1):
+    """spBayes's spDiag for an spMvGLM fit, on the device: {"DIC": {"bar.D", "D.bar.Omega", "pD", "DIC"},
+    "WAIC": {"lppd", "p.waic", "WAIC", "lconst"}} over iterations start..end (1-based, inclusive), every
+    thin-th, replayed from the chain the fit recorded (p.beta.theta.samples and p.w.samples).  The
+    definitions are in include/mk.h; the likelihood drops the binomial coefficient, "lconst" is what
+    full-likelihood figures add (-2 lconst to the deviance rows and WAIC, + lconst to lppd)."""
+    ses = sp_obj.get("_session")
+    if ses is None:
+        raise ValueError("error: the spMvGLM fit was closed; spDiag needs its recorded chain")
+    n_samples = sp_obj["_n_samples"]
+    end = n_samples if end is None else int(end)
+    start, thin = int(start), int(thin)
+    if not (1 <= start <= end <= n_samples):
+        raise ValueError("error: invalid start/end")
+    if thin < 1:
+        raise ValueError("error: invalid thin")
+    ses.set_kept_window(start, end)
+    c = ses.criteria(thin=thin)
+    row = dict(zip(c["names"], c["subsets"][0].tolist()))
+    return {"DIC": {k: row[k] for k in c["names"][:4]}, "WAIC": {k: row[k] for k in c["names"][4:]}}
+
+
 def spPredict(sp_obj, pred_coords, pred_covars=None, start=1, end=None, thin=1, diagnostics=False):
     """p.w.predictive.samples ((q n_test) x kept) for kept iterations start..end (1-based,
     inclusive; every thin-th), kriged from the chain states spMvGLM recorded (no refit).

@@ -64,6 +64,10 @@ def main():
                     help="chain diagnostics (ess, mcse, split R-hat per kept chain, on the device): one more JSON "
                          "line after the summary, {\"diagnostics\": convergence_report(...)}; one process (plain or "
                          "--devices)")
+    ap.add_argument("--criteria", action="store_true",
+                    help="model assessment (DIC and WAIC, accumulated on the device over the kept iterations): one "
+                         "more JSON line, {\"criteria\": the rows summed over the subsets}; one process (plain or "
+                         "--devices)")
     a = ap.parse_args()
     c = dict(CONFIGS[a.config])
     for k_arg, k_cfg in [("n", "n"), ("subsets", "K"), ("n_test", "n_test"), ("n_batch", "n_batch"),
@@ -77,6 +81,8 @@ def main():
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if a.diagnostics and world > 1:
         ap.error("--diagnostics runs in one process: plain, or over several GPUs with --devices")
+    if a.criteria and world > 1:
+        ap.error("--criteria runs in one process: plain, or over several GPUs with --devices")
     local = int(os.environ.get("LOCAL_RANK", "0"))
     dist = None
     if world > 1:
@@ -110,7 +116,8 @@ def main():
     if subs:
         # one process, fused kriging: x.test goes in as MK.R:87 passes it, p.predict comes out
         ses = mk.Session(subs, cfg, coords_test=d["coords_test"], subset_base=lo, device=local,
-                         x_test=d["x_test"] if (world == 1 and not big) else None)            # MK.R:108
+                         x_test=d["x_test"] if (world == 1 and not big) else None,            # MK.R:108
+                         criteria=a.criteria)
         for b in range(cfg.n_batch):          # progress every n.report = 10 batches (MK.R:84)
             ses.run(cfg.batch_length)
             if rank == 0 and (b + 1) % 10 == 0:
@@ -122,9 +129,11 @@ def main():
         dg = ("parameters" if big else True) if a.diagnostics else False
         out = (ses.outputs(quantiles=True, w_predict=not big, diagnostics=dg) if world == 1
                else {"parameters": [], "w_predict": []})
+        crit = ses.criteria() if a.criteria else None
     else:                                         # K < world: this rank has no subsets, it joins the exchange
         t3 = time.perf_counter()
         out = {"parameters": [], "w_predict": []}
+        crit = None
     t["fit_s"] = t3 - t2
     t["predict_quantiles_s"] = time.perf_counter() - t3
     diag = {k: v for k, v in out.items() if "_diag" in k}
@@ -209,6 +218,8 @@ def main():
         print(json.dumps(rec), flush=True)
         if a.diagnostics:
             print(json.dumps({"diagnostics": mk.convergence_report(diag)}), flush=True)
+        if a.criteria:
+            print(json.dumps({"criteria": dict(zip(crit["names"], crit["total"].tolist()))}), flush=True)
     if dist is not None:
         dist.destroy_process_group()
 
@@ -244,7 +255,7 @@ def node_main(a, c):
         d, K, q, cov_model=c["cov"], n_batch=c["n_batch"], batch_length=c["batch_length"], seed=a.seed,
         devices=devices, method=a.combine, predict_tile=c.get("predict_tile", 0), partition_method=a.partition,
         progress=progress, predictive=True,     # MK.R:87's x.test: the grids of p(y = 1) and result3
-        diagnostics=a.diagnostics)
+        diagnostics=a.diagnostics, criteria=a.criteria)
     ph["data_s"] = data_s
     rec = dict(config=a.config, workload=c, devices=devices, combine=a.combine, phases=ph,
                subset_iters_per_s=K * cfg.n_samples / ph["chains_s"])
@@ -258,6 +269,8 @@ def node_main(a, c):
     print(json.dumps(rec), flush=True)
     if a.diagnostics:
         print(json.dumps({"diagnostics": mk.convergence_report(summ["diagnostics"])}), flush=True)
+    if a.criteria:
+        print(json.dumps({"criteria": summ["criteria"]}), flush=True)
 
 
 if __name__ == "__main__":
