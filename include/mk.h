@@ -154,7 +154,8 @@ int mk_session_outputs(mk_session* s, mk_outputs* out);
 int mk_session_set_test_sites(mk_session* s, int32_t n_test, const double* coords_test);
 /* Covariates of the session's current test sites: x_test (q*n_test) x p column-major (spPredict's
  * pred.covars), copied to HBM; the p_* outputs and the p grids need them.  mk_session_set_test_sites
- * drops them (new sites need their own).  MK_E_ARG when the session has no test sites. */
+ * drops them (new sites need their own), and held-out data attached by mk_session_set_validation with
+ * them.  MK_E_ARG when the session has no test sites. */
 int mk_session_set_test_covars(mk_session* s, const double* x_test);
 int mk_session_set_kept_window(mk_session* s, int32_t first, int32_t last);
 /* After all iterations: the shard's 200-level grids, [n_subsets] x (200 x C) column-major -- which 0:
@@ -190,7 +191,9 @@ int mk_session_tile_grids_wp(mk_session* s, int32_t t0, double* out_w, double* o
  * difference; 14 the chain-diagnostic launches k_chain_diag / k_chain_diag_prob -- launches and ms,
  * timed whether or not profiling is on; 0 launches unless diagnostics were asked for; 15 the
  * model-assessment launches k_crit_accum / k_crit_replay / k_crit_finish / k_crit_total -- launches and
- * ms, always timed, 0 launches unless criteria were asked for).  Flops are algorithmic, not executed: GEMM tiles 2 m n k, the diagonal tile's
+ * ms, always timed, 0 launches unless criteria were asked for; 16 the held-out scoring launches
+ * k_score_cols / k_score_finish -- launches and ms, always timed, 0 launches unless validation data were
+ * attached).  Flops are algorithmic, not executed: GEMM tiles 2 m n k, the diagonal tile's
  * update as a SYRK, solves and inverse products over their triangles.  mk_session_profile(s, enable)
  * before mk_session_run: enable 0 = off, 1 = every kind, otherwise a mask with bit (1 + kind) per kind
  * bracketed (e.g. 2 << 0 = the panel update only; fewer events, less overhead). */
@@ -341,6 +344,71 @@ int mk_session_criteria(mk_session* s, int32_t thin, mk_criteria* out);
 int mk_meta_fit_ex(const mk_problem* prob, const mk_config* cfg, const int32_t* devices, int32_t n_devices,
                    mk_progress_fn progress, void* user, mk_outputs* out, mk_combined* comb, mk_diagnostics* diag,
                    mk_criteria* crit);
+
+/* ---- held-out validation: log score, Brier score and error rate at the test sites ----
+ * The out-of-sample companion of the model assessment above.  Held-out data are y_test and wt_test,
+ * q*n_test each, location-major like x_test: y successes of wt trials; a column with wt = 0 is "not
+ * observed here".  Per subset, over the kept states k = 1..n of the window and per test column c:
+ *   eta_kc = x_c' beta_k + w_kc and p_kc = linkinv(eta_kc): the predictive probabilities' own
+ *            expressions (p_pred_samples holds these p, bit for bit)
+ *   l_kc   = the chain's likelihood term of (y_c, wt_c) at eta_kc, the binomial coefficient dropped
+ *   pmean_c = (sum_k p_kc) / n, summed in time order from zero
+ *   lpd_c   = log((1/n) sum_k exp(l_kc)), by the streaming log-sum-exp (running maximum, scaled sum);
+ *             0 by itself where wt_c = 0
+ * and a row of MK_N_SCORE values:
+ *   n      columns with wt > 0
+ *   lpd    sum_c lpd_c
+ *   brier  (1/n) sum over wt_c > 0 of (pmean_c - y_c/wt_c)^2
+ *   err    the share of held-out trials the rule yhat_c = [pmean_c >= 0.5] gets wrong:
+ *          sum_c (yhat_c ? wt_c - y_c : y_c) / sum_c wt_c
+ *   lconst sum_c [lgamma(wt + 1) - lgamma(y + 1) - lgamma(wt - y + 1)]: what the likelihood terms
+ *          drop (0 for binary data); full-likelihood log scores add it, as with the criteria
+ * One thread owns a column and consumes its states in time order, so nothing in a column's pair depends
+ * on the tile, the stream group or the device block it ran in.  Sums over columns run in an order fixed
+ * by q*n_test alone (thread stride, then a fixed tree); the closing formulas use no contraction.  A
+ * non-finite draw makes that column's pair NaN and the subset's lpd, brier and err NaN; -inf is a
+ * legitimate lpd (an outcome the predictor gave probability 0); brier is NaN when n = 0 and err when
+ * no trial was held out.  Pointwise output per subset: (q*n_test) x 2 column-major, pmean_c and lpd_c;
+ * pmean is also the posterior mean map of p(y = 1).
+ * The combined posterior is a grid of levels (comb->result3, 200 of them): it is scored by the same
+ * formulas with the grid's n_rows levels as equally weighted states and p read, not computed:
+ *   l = y log p + (wt - y) log1p(-p), a term whose multiplier is 0 contributing 0. */
+#define MK_N_SCORE 5   /* rows: n, lpd, brier, err, lconst */
+typedef struct mk_validation { const double* y_test; const double* wt_test; } mk_validation;   /* q*n_test each */
+typedef struct mk_scores {            /* caller-allocated, any pointer may be NULL */
+  double* subsets;             /* [n_subsets] x 5 */
+  double* pointwise;           /* [n_subsets] x ((q*n_test) x 2) */
+  double* combined;            /* 5: the combined p grid's row (node call only) */
+  double* combined_pointwise;  /* (q*n_test) x 2 */
+} mk_scores;
+/* Attach held-out data to the session's current test sites (copied to HBM; NULL detaches and frees).
+ * Needs test sites and x_test, else MK_E_ARG; every entry must be finite with wt >= 0 and 0 <= y <= wt,
+ * else MK_E_ARG naming the first bad index.  A tiled session also gets its score buffer here and only
+ * here: 16 bytes per (subset, test column); MK_E_NOMEM names the remedies.  While data are attached,
+ * every tile replay of a tiled session -- mk_session_outputs, mk_session_tile_grids,
+ * mk_session_tile_grids_wp -- also scores that tile's columns into the buffer, from the same replay and
+ * over its kept window.  mk_session_set_test_sites detaches (the data belonged to the sites that go).
+ * Nothing is launched or allocated for scoring unless data are attached. */
+int mk_session_set_validation(mk_session* s, const mk_validation* val);
+/* After all iterations.  A fused session scores its kriging draws (all kept states) now.  A tiled
+ * session closes the rows from its buffer: MK_E_ARG, naming the first missing tile, if some tile has
+ * not been replayed over the current kept window since the data were attached.  combined and
+ * combined_pointwise are not written here. */
+int mk_session_scores(mk_session* s, mk_scores* out);
+/* The same scores of a grid of probabilities on the host: p is n_rows x n_cols column-major (e.g.
+ * comb->result3 with n_rows = 200), y and wt n_cols each (checked as above).  pointwise (n_cols x 2
+ * column-major) and row (5) may be NULL.  Columns are uploaded in chunks (bounded in bytes;
+ * MK_SCORE_CHUNK=<columns> overrides); the pairs of all columns stay in one device buffer and the row
+ * is reduced once, so nothing depends on the chunk. */
+int mk_score_grid(const double* p, int32_t n_rows, int64_t n_cols, const double* y, const double* wt,
+                  double* pointwise, double* row, int32_t device);
+/* mk_meta_fit_ex with held-out validation (mk_meta_fit_ex is this call with two NULLs): every block
+ * attaches the shared data and fills its subsets' rows and pairs at their global offsets;
+ * scores->combined / combined_pointwise come from mk_score_grid on comb->result3 (MK_E_ARG when that
+ * is not asked for).  Nothing is added to the exchange. */
+int mk_meta_fit_val(const mk_problem* prob, const mk_config* cfg, const int32_t* devices, int32_t n_devices,
+                    mk_progress_fn progress, void* user, mk_outputs* out, mk_combined* comb, mk_diagnostics* diag,
+                    mk_criteria* crit, const mk_validation* val, mk_scores* scores);
 
 /* ---- combine (MK.R:123-133): out = (grid_1 + ... + grid_K) / K, sequential order ---- */
 int mk_combine(const double* grids, int32_t K, int64_t grid_len, double* out, int32_t device);

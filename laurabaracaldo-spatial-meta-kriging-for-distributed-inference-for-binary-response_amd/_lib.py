@@ -27,6 +27,8 @@ N_LEVELS = 200
 N_DIAG = 3             # MK_N_DIAG: rows ess, mcse, rhat
 N_CRIT = 8             # MK_N_CRIT: the rows of mk_criteria, in CRIT_NAMES' order
 CRIT_NAMES = ["bar.D", "D.bar.Omega", "pD", "DIC", "lppd", "p.waic", "WAIC", "lconst"]
+N_SCORE = 5            # MK_N_SCORE: the rows of mk_scores, in SCORE_NAMES' order
+SCORE_NAMES = ["n", "lpd", "brier", "err", "lconst"]
 
 _dp = ctypes.POINTER(ctypes.c_double)
 _ip = ctypes.POINTER(ctypes.c_int32)
@@ -83,6 +85,14 @@ class Criteria(ctypes.Structure):
     _fields_ = [("subsets", _dp), ("total", _dp), ("pointwise", _dp)]
 
 
+class Validation(ctypes.Structure):
+    _fields_ = [("y_test", _dp), ("wt_test", _dp)]
+
+
+class Scores(ctypes.Structure):
+    _fields_ = [("subsets", _dp), ("pointwise", _dp), ("combined", _dp), ("combined_pointwise", _dp)]
+
+
 # int (*mk_progress_fn)(void* user, int32_t iterations, int32_t n_samples)
 PROGRESS_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32)
 
@@ -90,6 +100,13 @@ EXPORTS = {
     "mk_meta_fit_ex": (ctypes.c_int, [ctypes.POINTER(Problem), ctypes.POINTER(Config), _ip, ctypes.c_int32,
                                       PROGRESS_FN, ctypes.c_void_p, ctypes.POINTER(Outputs), ctypes.POINTER(Combined),
                                       ctypes.POINTER(Diagnostics), ctypes.POINTER(Criteria)]),
+    "mk_meta_fit_val": (ctypes.c_int, [ctypes.POINTER(Problem), ctypes.POINTER(Config), _ip, ctypes.c_int32,
+                                       PROGRESS_FN, ctypes.c_void_p, ctypes.POINTER(Outputs), ctypes.POINTER(Combined),
+                                       ctypes.POINTER(Diagnostics), ctypes.POINTER(Criteria), ctypes.POINTER(Validation),
+                                       ctypes.POINTER(Scores)]),
+    "mk_session_set_validation": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(Validation)]),
+    "mk_session_scores": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(Scores)]),
+    "mk_score_grid": (ctypes.c_int, [_dp, ctypes.c_int32, ctypes.c_int64, _dp, _dp, _dp, _dp, ctypes.c_int32]),
     "mk_session_set_criteria": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32]),
     "mk_session_criteria": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(Criteria)]),
     "mk_meta_fit": (ctypes.c_int, [ctypes.POINTER(Problem), ctypes.POINTER(Config), _ip, ctypes.c_int32,

@@ -103,12 +103,20 @@ __device__ inline double loglik_term(double y, double wt, double eta, int link) 
 // in column order j = 0..p-1 from zero, then the link's inverse (k_post_prob's expressions).
 // xrow: the row's first covariate, columns ldx apart.  Every user of p calls this one function, so
 // the quantile grids and the draws agree bit for bit.
-__device__ inline double pred_prob(const double* __restrict__ xrow, long ldx, const double* __restrict__ beta, int p,
-                                   double w, int link) {
+// pred_eta and pred_linkinv are its two halves: the held-out scores (mk_scores.hip) need eta for the
+// likelihood term and p for the predictive mean of the same draw, from the same expressions.
+__device__ inline double pred_eta(const double* __restrict__ xrow, long ldx, const double* __restrict__ beta, int p,
+                                  double w) {
   double acc = 0.0;
   for (int j = 0; j < p; ++j) acc = fma(xrow[(long)j * ldx], beta[j], acc);
-  const double eta = acc + w;
+  return acc + w;
+}
+__device__ inline double pred_linkinv(double eta, int link) {
   return (link == MK_LINK_PROBIT) ? norm_cdf(eta) : 1.0 / (1.0 + exp(-eta));
+}
+__device__ inline double pred_prob(const double* __restrict__ xrow, long ldx, const double* __restrict__ beta, int p,
+                                   double w, int link) {
+  return pred_linkinv(pred_eta(xrow, ldx, beta, p, w), link);
 }
 
 // spBayes util logitInv(z, a, b) = b - (b-a)/(1+exp(z))

@@ -130,6 +130,11 @@ __global__ void k_crit_accum(Model md, Crit c, int kidx);
 __global__ void k_crit_replay(Model md, Crit c, int first, int n, int thin);
 __global__ void k_crit_finish(Model md, Crit c, int n, double* rows, double* pointwise);
 __global__ void k_crit_total(const double* rows, int S, double* out);
+// mk_scores.hip
+template <bool GRID>
+__global__ void k_score_cols(const double* data, long subset_stride, long row_stride, long col_stride, int n, int n_cols,
+                             ProbSrc ps, const double* y, const double* wt, long col0, long C, double* pw);
+__global__ void k_score_finish(const double* pw, const double* y, const double* wt, long C, double* rows);
 // mk_post.hip
 __global__ void k_weiszfeld(const double* grids, int K, int L, long C, int max_iter, double tol, double* out, int* iters);
 __global__ void k_post_index(uint64_t seed, int samplesize, int n_levels, int* idx);

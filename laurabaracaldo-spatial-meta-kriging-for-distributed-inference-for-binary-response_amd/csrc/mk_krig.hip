@@ -113,6 +113,7 @@ extern "C" int mk_session_set_test_sites(mk_session* s, int32_t n_test, const do
   HIPCHK(hipStreamSynchronize(s->stream));
   s->diag_on = false;                      // a diagnostics sink was sized for the sites that go
   s->diag_sink = mk_diagnostics{};
+  validation_detach(s);                    // held-out data belonged to the sites that go
   int rc = set_test_covars(s, nullptr);   // the covariates belonged to the sites that go
   if (rc) return rc;
   return kriging_buffers(s, n_test, coords_test);
@@ -220,6 +221,11 @@ static int tile_outputs(mk_session* s, int t0, double* dq, double* dqp, mk_outpu
   // an attached diagnostics sink: this tile's columns, while its draws exist (no second replay)
   if (s->diag_on) {
     const int rc = tile_diagnostics(s, t0, n_kept, Ct);
+    if (rc) return rc;
+  }
+  // attached validation data: this tile's columns of the held-out scores, from the same draws
+  if (s->val.on) {
+    const int rc = tile_scores(s, t0, n_kept, Ct);
     if (rc) return rc;
   }
   HIPCHK(hipStreamSynchronize(st));

@@ -403,6 +403,12 @@ extern "C" int mk_meta_fit_diag(const mk_problem* pr, const mk_config* c, const 
 extern "C" int mk_meta_fit_ex(const mk_problem* pr, const mk_config* c, const int32_t* devices, int32_t G,
                               mk_progress_fn progress, void* user, mk_outputs* out, mk_combined* comb,
                               mk_diagnostics* diag, mk_criteria* crit) {
+  return mk_meta_fit_val(pr, c, devices, G, progress, user, out, comb, diag, crit, nullptr, nullptr);
+}
+
+extern "C" int mk_meta_fit_val(const mk_problem* pr, const mk_config* c, const int32_t* devices, int32_t G,
+                               mk_progress_fn progress, void* user, mk_outputs* out, mk_combined* comb,
+                               mk_diagnostics* diag, mk_criteria* crit, const mk_validation* val, mk_scores* scores) {
   if (!pr || !c) return fail(MK_E_ARG, "null problem/config");
   if (!devices || G < 1) return fail(MK_E_ARG, "n_devices must be >= 1 with a device list");
   const int K = pr->n_subsets;
@@ -425,6 +431,13 @@ extern "C" int mk_meta_fit_ex(const mk_problem* pr, const mk_config* c, const in
   const bool dg_p = diag && (diag->p_predict || diag->p_predict_worst);
   if (dg_p && !pr->x_test) return fail(MK_E_ARG, "p_predict diagnostics need x_test");
   const bool want_crit = crit && (crit->subsets || crit->total || crit->pointwise);
+  const bool sc_comb = scores && (scores->combined || scores->combined_pointwise);
+  const bool sc_sub = scores && (scores->subsets || scores->pointwise);
+  const bool want_val = sc_comb || sc_sub;
+  if (want_val && (!val || !val->y_test || !val->wt_test)) return fail(MK_E_ARG, "held-out scores need validation data");
+  if (want_val && (!pr->x_test || pr->n_test < 1)) return fail(MK_E_ARG, "held-out scores need test sites and x_test");
+  if (sc_comb && !(comb && comb->result3))
+    return fail(MK_E_ARG, "the combined grid's scores are those of comb->result3: ask for it");
   const int q = pr->q, p = pr->p, n_samples = c->n_batch * c->batch_length;
   if (c->n_batch < 1 || c->batch_length < 1) return fail(MK_E_ARG, "n.batch and batch.length must be >= 1");
 
@@ -467,8 +480,9 @@ extern "C" int mk_meta_fit_ex(const mk_problem* pr, const mk_config* c, const in
     sp.x = pr->x + s0 * q * p;
     mk_config sc = *c;
     sc.device = x.dev;
-    const int e = mk_session_create(&sp, &sc, &x.ses);
-    return (e || !want_crit) ? e : mk_session_set_criteria(x.ses, 1);
+    int e = mk_session_create(&sp, &sc, &x.ses);
+    if (e || (want_crit && (e = mk_session_set_criteria(x.ses, 1)))) return e;
+    return sc_sub ? mk_session_set_validation(x.ses, val) : 0;
   });
   if (rc) return rc;
   if (nd.use_rccl) {
@@ -628,7 +642,7 @@ extern "C" int mk_meta_fit_ex(const mk_problem* pr, const mk_config* c, const in
     const PredKind pk{GRID_P, out ? out->p_predict : nullptr, out ? out->p_predict_sum : nullptr,
                       comb ? comb->result3 : nullptr, &Block::grids_p};
     const bool draws = out && (out->w_pred_samples || out->p_pred_samples);
-    const bool replay = tiled && (w.asked() || pk.asked() || draws || dg_w || dg_p);   // one replay per tile serves them all
+    const bool replay = tiled && (w.asked() || pk.asked() || draws || dg_w || dg_p || sc_sub);   // one replay per tile serves them all
     if (!tiled) {
       for (const PredKind* k : {&pk, &w})   // p before w
         if (k->asked() && (rc = whole_grids(k->kind, C, k->h_each, k->h_comb, k->h_sum))) return rc;
@@ -667,6 +681,23 @@ extern "C" int mk_meta_fit_ex(const mk_problem* pr, const mk_config* c, const in
       }
     }
   }
+  // ---- held-out validation (optional): every block closes its subsets' rows and pairs at their global
+  // offsets -- a fused block scores its draws now, a tiled one was scored by the tile replays above; the
+  // combined p grid is scored from the host copy the combine just wrote
+  if (sc_sub && n_test > 0) {
+    rc = nd.pool->run([&](int r) -> int {
+      Block& x = *nd.b[r];
+      if (!x.ses) return 0;
+      mk_scores sc{};
+      if (scores->subsets) sc.subsets = scores->subsets + (size_t)x.lo * MK_N_SCORE;
+      if (scores->pointwise) sc.pointwise = scores->pointwise + (size_t)x.lo * 2 * C;
+      return mk_session_scores(x.ses, &sc);
+    });
+    if (rc) return rc;
+  }
+  if (sc_comb && (rc = mk_score_grid(comb->result3, L, C, val->y_test, val->wt_test, scores->combined_pointwise,
+                                     scores->combined, devices[0])))
+    return rc;
   if (diag) {   // the worst rows over all K: the blocks' own, folded here
     bool first = true;
     for (int r = 0; r < G; ++r) {

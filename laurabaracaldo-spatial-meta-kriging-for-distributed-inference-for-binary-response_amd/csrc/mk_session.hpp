@@ -8,6 +8,7 @@
 //   mk_parity.hip    parity-test entry points
 //   mk_diag.hip      chain diagnostics: the launcher, the session entry points, the tile sink
 //   mk_criteria.hip  model assessment (DIC, WAIC): the kernels, the scratch, the session entry points
+//   mk_scores.hip    held-out validation (log score, Brier, error rate): the kernels, the entry points
 //
 // mk_internal.hpp stays the interface towards mk_multi.hip and mk_watch.hip.
 #pragma once
@@ -48,7 +49,7 @@ static inline int env_int(const char* name, int dflt) {
   return (v && *v) ? std::atoi(v) : dflt;
 }
 
-constexpr int NKSTAT = 16;
+constexpr int NKSTAT = 17;
 // KS_CHOL_UPDATE: the 128-tile panel-update launches (k_chol_update<128>); KS_CHOL_UPDATE_SUB:
 // the 64- / 32-sub-tile ones (small grids).  Together: the roofline kernel k_chol_update.
 // KS_UPDATE_BUSY: both, with the time of launches that overlap (the split schedule's bulk and
@@ -57,7 +58,8 @@ constexpr int NKSTAT = 16;
 // bound: only the pairs whose factor changed are in the list -- bench_kriging counts exactly).
 // KS_COV: the candidates' covariance assembly (k_cov_candidate, with k_matern_table for Matern).
 enum { KS_CHOL_UPDATE = 0, KS_CHOL_DIAG, KS_CHOL_TRSM, KS_SWEEP, KS_LAUUM, KS_ITER, KS_INV, KS_CHOL_UPDATE_SUB,
-       KS_UPDATE_BUSY, KS_PRED_VAR, KS_COV, KS_SWEEP_FALLBACK, KS_KRIG_CHEB, KS_KRIG_FALLBACK, KS_DIAG, KS_CRIT };
+       KS_UPDATE_BUSY, KS_PRED_VAR, KS_COV, KS_SWEEP_FALLBACK, KS_KRIG_CHEB, KS_KRIG_FALLBACK, KS_DIAG, KS_CRIT,
+       KS_SCORE };
 // KS_KRIG_CHEB: tiles kriged by phi interpolation (predict_tile_cheb): launches = tiles, flops = exact
 // s evaluations ((subset, node or check point) pairs), total_ms = the largest check difference seen
 // (not a time).  KS_KRIG_FALLBACK: tiles whose check failed and were replayed exactly (launches), and
@@ -67,6 +69,9 @@ enum { KS_CHOL_UPDATE = 0, KS_CHOL_DIAG, KS_CHOL_TRSM, KS_SWEEP, KS_LAUUM, KS_IT
 // KS_CRIT: the model-assessment launches (k_crit_accum per kept iteration and stream group, k_crit_replay,
 // k_crit_finish and k_crit_total per mk_session_criteria), bracketed by events whether or not the profiler
 // is on; none are made unless criteria were asked for.
+// KS_SCORE: the held-out scoring launches (k_score_cols per tile replay or mk_session_scores, k_score_finish
+// per mk_session_scores), bracketed by events whether or not the profiler is on; none are made unless
+// validation data were attached.
 // KS_SWEEP_FALLBACK: launches = (subset, iteration) sweeps k_sweep_mg refused admission and its
 // k_sweep fallback ran (counted on the device, read at the end of every mk_session_run; no timing).
 
@@ -225,6 +230,17 @@ struct Criteria {
   int win_lo = 0, win_n = -1;
 };
 
+// mk_scores.hip.  Held-out validation (mk_session_set_validation): the data in HBM and, for a tiled
+// session, the pointwise pairs its tile replays fill (allocated when data are attached, never otherwise).
+struct Validation {
+  bool on = false;
+  double* y = nullptr;        // [q n_test_all]
+  double* wt = nullptr;       // [q n_test_all]
+  double* pw = nullptr;       // tiled: [S][2][q n_test_all], plane 0 pmean_c, plane 1 lpd_c
+  std::vector<char> done;     // tiled: per tile, replayed since the data were attached
+  int lo = -1, n = -1;        // the kept window those replays ran over
+};
+
 }  // namespace mk
 
 struct mk_session {
@@ -262,6 +278,7 @@ struct mk_session {
   mk::SweepPlan sweep;
   mk::Profiler prof;
   mk::Criteria crit;
+  mk::Validation val;
   mk_diagnostics diag_sink{};           // mk_session_set_diagnostics: filled by every tile replay while diag_on
   bool diag_on = false;
   hipError_t launch_err = hipSuccess;   // first failed kernel launch of a run
@@ -384,5 +401,12 @@ int tile_diagnostics(mk_session* s, int t0, int n_kept, int Ct);
 void launch_crit_accum(mk_session* s, Group& g, int kidx);
 // The events of the launches above: priced into KS_CRIT (price = false: only destroyed).  The streams are idle.
 void crit_drain(mk_session* s, bool price);
+
+// ---- mk_scores.hip
+// Attached validation data's share of tile [t0, ..): scores the draws in md.w_pred ([S][n_kept][Ct]) into
+// the session's pair buffer.  Timed as KS_SCORE; returns after the stream is idle.
+int tile_scores(mk_session* s, int t0, int n_kept, int Ct);
+// Frees the validation data and the pair buffer (mk_session_set_test_sites; NULL data).
+void validation_detach(mk_session* s);
 
 }  // namespace mk

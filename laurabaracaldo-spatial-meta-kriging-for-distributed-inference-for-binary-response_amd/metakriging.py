@@ -90,14 +90,16 @@ def r_sample_replace(n, size, seed):
 
 def meta_fit(y, x, weight, coords, q, index_part, coords_test=None, cfg=None, subset_base=0, device=0,
              cov_model="exponential", n_batch=100, batch_length=50, seed=20250114, x_test=None, diagnostics=False,
-             criteria=False):
+             criteria=False, y_test=None, weights_test=1):
     """All subsets of one shard on one GPU; returns the list `obj` of MK.R:108 for those subsets:
     [{'parameters': 200 x P, 'w.predict': 200 x (q n_test)}, ...]; with x_test (MK.R:87's x.test) each
     also holds 'p.predict' (200 x (q n_test)): the grid of p(y = 1) at the test sites.
     diagnostics=True: each also holds 'parameters.diagnostics' (3 x P: ess, mcse, split R-hat of its kept
     chain) and, with test sites, 'w.predict.diagnostics' / 'p.predict.diagnostics' (3 x (q n_test)).
     criteria=True: each also holds 'criteria', the subset's DIC and WAIC rows by name (bar.D, D.bar.Omega,
-    pD, DIC, lppd, p.waic, WAIC, lconst; Session.criteria), accumulated in chain over its kept states."""
+    pD, DIC, lppd, p.waic, WAIC, lconst; Session.criteria), accumulated in chain over its kept states.
+    y_test (with weights_test trials; needs x_test): each also holds 'scores', the subset's held-out row by
+    name (n, lpd, brier, err, lconst; Session.scores) of its posterior predictive at the test sites."""
     p = np.asarray(x).shape[1]
     if cfg is None:
         beta0, bt = start_values(y, x, weight, q)
@@ -106,9 +108,12 @@ def meta_fit(y, x, weight, coords, q, index_part, coords_test=None, cfg=None, su
     subsets = [subset_data(y, x, weight, coords, q, idx) for idx in index_part]
     with Session(subsets, cfg, coords_test=coords_test, subset_base=subset_base, device=device, x_test=x_test,
                  criteria=criteria) as ses:
+        if y_test is not None:
+            ses.set_validation(y_test, weights_test)
         ses.run(cfg.n_samples)
         out = ses.outputs(diagnostics=diagnostics)
         crit = ses.criteria() if criteria else None
+        scores = ses.scores() if y_test is not None else None
     res = []
     for i in range(len(subsets)):
         d = {"parameters": out["parameters"][i]}
@@ -121,6 +126,8 @@ def meta_fit(y, x, weight, coords, q, index_part, coords_test=None, cfg=None, su
                 d[kind.replace("_", ".") + ".diagnostics"] = out[kind + "_diag"][i]
         if crit is not None:
             d["criteria"] = dict(zip(crit["names"], crit["subsets"][i].tolist()))
+        if scores is not None:
+            d["scores"] = dict(zip(scores["names"], scores["subsets"][i].tolist()))
         res.append(d)
     return res
 
@@ -196,6 +203,52 @@ def convergence_report(diag, ess_min=100, rhat_max=1.05):
     return rep
 
 
+def median_subset_row(scores):
+    """The row (by name) of the subset whose lpd is the median of the K subsets' (of an even K the better of
+    the two middle ones; subsets with a NaN lpd last): the "typical subset posterior" the combined one is compared
+    with."""
+    lpd = np.asarray(scores["subsets"])[:, 1]
+    order = np.argsort(np.where(np.isnan(lpd), np.inf, -lpd), kind="stable")      # best first, NaN last
+    i = int(order[(len(order) - 1) // 2])
+    row = dict(zip(scores["names"], np.asarray(scores["subsets"])[i].tolist()))
+    row["subset"] = i
+    return row
+
+
+def validation_report(pmean, y, weights=1, bins=10):
+    """Host-side companions of the held-out scores, from a pointwise pmean (NumPy): 'auc', the area under
+    the ROC curve by the Mann-Whitney statistic with ties counted half, over the columns with weights = 1
+    (None unless both outcomes occur there); and the reliability table over `bins` equal-width bins of
+    pmean on the columns with weights > 0 -- 'bin_edges', and per bin 'count', 'mean_pmean' and
+    'mean_observed' (the mean of y / weights; NaN for an empty bin)."""
+    pm = np.asarray(pmean, dtype=np.float64).reshape(-1)
+    yv = np.asarray(y, dtype=np.float64).reshape(-1)
+    wt = np.broadcast_to(np.asarray(weights, dtype=np.float64), pm.shape)
+    if yv.shape != pm.shape:
+        raise ValueError("error: pmean and y must have the same length")
+    one = (wt == 1.0) & np.isfinite(pm)
+    pos, neg = pm[one & (yv == 1.0)], pm[one & (yv == 0.0)]
+    auc = None
+    if pos.size and neg.size:
+        allv = np.concatenate([pos, neg])
+        order = np.argsort(allv, kind="stable")
+        ranks = np.empty(allv.size)
+        sv = allv[order]
+        start = np.flatnonzero(np.concatenate([[True], sv[1:] != sv[:-1]]))
+        end = np.concatenate([start[1:], [sv.size]])
+        for a, b in zip(start, end):                          # mid-ranks: ties count half
+            ranks[order[a:b]] = 0.5 * (a + b - 1) + 1.0
+        auc = float((ranks[:pos.size].sum() - pos.size * (pos.size + 1) / 2.0) / (pos.size * neg.size))
+    obs = (wt > 0.0) & np.isfinite(pm)
+    edges = np.linspace(0.0, 1.0, int(bins) + 1)
+    which = np.clip(np.digitize(pm[obs], edges[1:-1]), 0, int(bins) - 1)
+    count = np.bincount(which, minlength=int(bins)).astype(np.int64)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        mean_p = np.bincount(which, weights=pm[obs], minlength=int(bins)) / count
+        mean_o = np.bincount(which, weights=yv[obs] / wt[obs], minlength=int(bins)) / count
+    return dict(auc=auc, bin_edges=edges, count=count, mean_pmean=mean_p, mean_observed=mean_o)
+
+
 def posterior_summary(result, result2, x_test, q=None, samplesize=1000, seed=20250114, device=0, rng="philox",
                       index=None, link="logit"):
     """MK.R:136-165 on device: interpolate both combined grids to Xout (996 levels), one shared
@@ -209,7 +262,7 @@ def posterior_summary(result, result2, x_test, q=None, samplesize=1000, seed=202
 
 def reference_flow(d, K, q, cov_model="exponential", n_batch=100, batch_length=50, seed=20250114, devices=(0,),
                    method="mean", predict_tile=0, partition_method="R", samplesize=1000, progress=None,
-                   predictive=False, diagnostics=False, criteria=False):
+                   predictive=False, diagnostics=False, criteria=False, validate=False):
     """The reference script end to end in one process over the GPUs in `devices` (mk_meta_fit: the
     subsets sharded over them in-library, the combine device to device):
 
@@ -227,6 +280,10 @@ def reference_flow(d, K, q, cov_model="exponential", n_batch=100, batch_length=5
     (the '*_diag_worst' arrays of meta_fit_node; convergence_report reads them).
     criteria=True: the DIC and WAIC rows summed over the K subsets come back by name as
     summary["criteria"] (meta_fit_node's 'criteria' total).
+    validate=True (implies predictive): d["y_test"] is scored at the test sites; summary["validation"]
+    holds 'combined' (the combined p grid's row by name), 'subsets' (K x 5), 'names', 'median_subset'
+    (the row of the subset whose lpd is the median of the K) and 'report' (validation_report of the
+    combined grid's pmean: AUC and the reliability table).
     Returns (phases, result, result2, summary, cfg) -- phases in seconds of
     wall clock: set-up (partition, glm, subset slicing), the chains (to the last batch boundary),
     quantiles + combine, post-processing, and the whole."""
@@ -251,8 +308,9 @@ def reference_flow(d, K, q, cov_model="exponential", n_batch=100, batch_length=5
         return bool(progress(it, n_samples)) if progress is not None else False
 
     fit = meta_fit_node(subs, cfg, coords_test=d["coords_test"], devices=devices, method=method, per_subset=False,
-                        progress=_progress, x_test=d["x_test"] if predictive else None,
-                        diagnostics=diagnostics, criteria=criteria)                         # MK.R:100-133
+                        progress=_progress, x_test=d["x_test"] if predictive or validate else None,
+                        diagnostics=diagnostics, criteria=criteria,
+                        validation=dict(y_test=d["y_test"], pointwise=True) if validate else None)   # MK.R:100-133
     t3 = time.perf_counter()
     t["chains_s"] = stamp.get("chains", t3) - t1
     t["quantiles_combine_s"] = t3 - stamp.get("chains", t3)
@@ -266,6 +324,11 @@ def reference_flow(d, K, q, cov_model="exponential", n_batch=100, batch_length=5
         summ["diagnostics"] = {k: v for k, v in fit.items() if k.endswith("_diag_worst")}
     if criteria:
         summ["criteria"] = dict(zip(fit["criteria"]["names"], fit["criteria"]["total"].tolist()))
+    if validate:
+        sc = fit["scores"]
+        summ["validation"] = dict(combined=sc["combined"], subsets=sc["subsets"], names=sc["names"],
+                                  median_subset=median_subset_row(sc),
+                                  report=validation_report(sc["combined_pointwise"][:, 0], d["y_test"]))
     t["end_to_end_s"] = time.perf_counter() - t0
     t["exchange"] = fit["exchange"]          # the combine's all-to-all: "rccl" (distinct GPUs) or "copy"
     t["comm_ranks"] = fit["comm_ranks"]      # ranks RCCL's communicators hold (copies: device blocks)

@@ -15,7 +15,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import Combined, check
-from .outbuf import CriteriaBuffers, DiagnosticBuffers, OutputBuffers
+from .outbuf import CriteriaBuffers, DiagnosticBuffers, OutputBuffers, ScoreBuffers, validation_arrays
 from .session import PackedProblem
 
 N_LEVELS = _lib.N_LEVELS
@@ -24,7 +24,7 @@ N_LEVELS = _lib.N_LEVELS
 def meta_fit_node(subsets, cfg, coords_test=None, devices=(0,), subset_base=0, method="mean", per_subset=True,
                   samples=False, w_samples=False, w_pred_samples=False, acceptance=False, w_predict_sum=False,
                   progress=None, record_w=False, max_iter=100, tol=1e-12, x_test=None, p_pred_samples=False,
-                  p_predict_sum=False, diagnostics=False, criteria=False):
+                  p_predict_sum=False, diagnostics=False, criteria=False, validation=None):
     """Fit all subsets over `devices` and combine.  Returns a dict with 'result' (200 x P, MK.R:127),
     'result2' (200 x q n_test, MK.R:133; None without test sites), 'exchange' ('rccl' / 'copy'),
     'comm_ranks' (the ranks the exchange spans: RCCL's own ncclCommCount, or the blocks for copies),
@@ -38,7 +38,12 @@ def meta_fit_node(subsets, cfg, coords_test=None, devices=(0,), subset_base=0, m
     (per subset 3 x C: ess, mcse, split R-hat) -- and the '*_diag_worst' arrays (3 x C) over all K.
     criteria=True (mk_meta_fit_ex) adds 'criteria': Session.criteria's dict for all K subsets -- 'subsets'
     (K x 8: bar.D, D.bar.Omega, pD, DIC, lppd, p.waic, WAIC, lconst), 'total' (their sums in global
-    subset order) and 'names'; criteria="pointwise" also the per-observation pairs."""
+    subset order) and 'names'; criteria="pointwise" also the per-observation pairs.
+    validation (mk_meta_fit_val): held-out outcomes at the test sites -- y_test, (y_test, weights_test) or
+    a dict with 'y_test' and optionally 'weights_test' and 'pointwise' -- adds 'scores': Session.scores'
+    dict for all K subsets ('subsets' K x 5: n, lpd, brier, err, lconst; 'names') plus 'combined', the row
+    of the combined p grid result3 by name (score_grid's); with pointwise also the 'pointwise' pairs per
+    subset and 'combined_pointwise'.  Needs x_test."""
     lib = _lib.load()
     if method not in ("mean", "median"):
         raise ValueError(f"error: unknown combine method '{method}'")
@@ -77,9 +82,23 @@ def meta_fit_node(subsets, cfg, coords_test=None, devices=(0,), subset_base=0, m
         kinds = ["parameters"] + (["w_predict"] if have else []) + (["p_predict"] if have_x else [])
         db = DiagnosticBuffers(K, cfg, n_test, {k + sfx for k in kinds for sfx in ("_diag", "_diag_worst")})
     kb = CriteriaBuffers(K, q, pp.n_part, pointwise=criteria == "pointwise") if criteria else None
-    check(lib.mk_meta_fit_ex(ctypes.byref(pp.c), ctypes.byref(c), devs.ctypes.data_as(_lib._ip), len(devs), fn, None,
-                             ctypes.byref(ob.c), ctypes.byref(cb), ctypes.byref(db.c) if db is not None else None,
-                             ctypes.byref(kb.c) if kb is not None else None))
+    sb = val = None
+    if validation is not None:
+        if not have_x:
+            raise ValueError("error: validation needs test sites and x_test")
+        if isinstance(validation, dict):
+            vy, vw, vpw = validation["y_test"], validation.get("weights_test", 1), validation.get("pointwise", False)
+        elif isinstance(validation, tuple):
+            (vy, vw), vpw = validation, False
+        else:
+            vy, vw, vpw = validation, 1, False
+        val = validation_arrays(vy, vw, C)
+        sb = ScoreBuffers(K, C, pointwise=bool(vpw), combined=True)
+    check(lib.mk_meta_fit_val(ctypes.byref(pp.c), ctypes.byref(c), devs.ctypes.data_as(_lib._ip), len(devs), fn, None,
+                              ctypes.byref(ob.c), ctypes.byref(cb), ctypes.byref(db.c) if db is not None else None,
+                              ctypes.byref(kb.c) if kb is not None else None,
+                              ctypes.byref(val[2]) if val is not None else None,
+                              ctypes.byref(sb.c) if sb is not None else None))
     del keep
     out = {"result": result.T.copy(), "result2": None if result2 is None else result2.T.copy(),
            "exchange": "rccl" if cb.exchange else "copy", "comm_ranks": int(cb.comm_ranks)}
@@ -90,4 +109,6 @@ def meta_fit_node(subsets, cfg, coords_test=None, devices=(0,), subset_base=0, m
         out.update(db.unpack())
     if kb is not None:
         out["criteria"] = kb.unpack()
+    if sb is not None:
+        out["scores"] = sb.unpack()
     return out

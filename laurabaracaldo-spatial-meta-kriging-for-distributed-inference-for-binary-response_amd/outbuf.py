@@ -2,7 +2,8 @@
 caller's layouts: one table of field -> shape serves Session.outputs and meta_fit_node."""
 import numpy as np
 
-from ._lib import CRIT_NAMES, N_CRIT, N_DIAG, N_LEVELS, Criteria, Diagnostics, Outputs, dptr
+from ._lib import (CRIT_NAMES, N_CRIT, N_DIAG, N_LEVELS, N_SCORE, SCORE_NAMES, Criteria, Diagnostics, Outputs, Scores,
+                   Validation, dptr)
 
 # The array libmk fills for each mk_outputs field, row-major, in terms of: K subsets, P parameters,
 # C = q n_test kriging columns, L levels, n = n_samples, kept states, B amcmc batches, R = P + 1
@@ -112,4 +113,43 @@ class CriteriaBuffers:
             for N in self.n_obs:                              # column-major (n_s q) x 2 per subset
                 out["pointwise"].append(self.pointwise[off:off + 2 * N].reshape(2, N).T.copy())
                 off += 2 * N
+        return out
+
+
+def validation_arrays(y_test, weights_test, C):
+    """Held-out data as libmk reads them: (y, wt, the mk_validation pointing at them), each q*n_test
+    long, location-major; weights_test broadcasts (1: binary outcomes)."""
+    y = np.ascontiguousarray(np.asarray(y_test, dtype=np.float64).reshape(-1))
+    if y.shape != (int(C),):
+        raise ValueError(f"error: y_test must have q*n_test = {int(C)} entries, not {y.size}")
+    wt = np.ascontiguousarray(np.broadcast_to(np.asarray(weights_test, dtype=np.float64), (int(C),)))
+    v = Validation()
+    v.y_test, v.wt_test = dptr(y), dptr(wt)
+    return y, wt, v
+
+
+class ScoreBuffers:
+    """The arrays behind an mk_scores of K subsets with C = q n_test test columns: `.c` points at them;
+    unpack() gives {'subsets': (K, 5), 'names': the rows' names} and, with pointwise, 'pointwise': per
+    subset a C x 2 array, columns pmean_c and lpd_c; with combined, 'combined' (the combined p grid's
+    row by name) and, with pointwise too, 'combined_pointwise' (C x 2)."""
+
+    def __init__(self, K, C, pointwise=False, combined=False):
+        self.K, self.C = int(K), int(C)
+        self.subsets = np.zeros((self.K, N_SCORE))
+        self.pointwise = np.zeros((self.K, 2, self.C)) if pointwise else None
+        self.combined = np.zeros(N_SCORE) if combined else None
+        self.combined_pointwise = np.zeros((2, self.C)) if combined and pointwise else None
+        self.c = Scores()
+        self.c.subsets, self.c.pointwise = dptr(self.subsets), dptr(self.pointwise)
+        self.c.combined, self.c.combined_pointwise = dptr(self.combined), dptr(self.combined_pointwise)
+
+    def unpack(self):
+        out = {"subsets": self.subsets.copy(), "names": list(SCORE_NAMES)}
+        if self.pointwise is not None:
+            out["pointwise"] = [self.pointwise[i].T.copy() for i in range(self.K)]
+        if self.combined is not None:
+            out["combined"] = dict(zip(SCORE_NAMES, self.combined.tolist()))
+        if self.combined_pointwise is not None:
+            out["combined_pointwise"] = self.combined_pointwise.T.copy()
         return out

@@ -10,7 +10,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import Config, Problem, check, dptr, iptr
-from .outbuf import CriteriaBuffers, DiagnosticBuffers, OutputBuffers
+from .outbuf import CriteriaBuffers, DiagnosticBuffers, OutputBuffers, ScoreBuffers, validation_arrays
 
 COV_MODELS = {"exponential": _lib.MK_COV_EXPONENTIAL, "matern": _lib.MK_COV_MATERN}
 LINKS = {"logit": _lib.MK_LINK_LOGIT, "probit": _lib.MK_LINK_PROBIT}
@@ -20,6 +20,7 @@ LINKS = {"logit": _lib.MK_LINK_LOGIT, "probit": _lib.MK_LINK_PROBIT}
  KS_PRED_VAR, KS_COV, KS_SWEEP_FALLBACK, KS_KRIG_CHEB, KS_KRIG_FALLBACK) = range(14)
 KS_DIAG = 14      # the chain-diagnostic launches (always timed; 0 launches unless diagnostics were asked for)
 KS_CRIT = 15      # the model-assessment launches (always timed; 0 launches unless criteria were asked for)
+KS_SCORE = 16     # the held-out scoring launches (always timed; 0 launches unless validation data were attached)
 
 
 def _f64(a):
@@ -303,6 +304,30 @@ class Session:
         check(self._lib.mk_session_criteria(self._h, int(thin), ctypes.byref(cb.c)))
         return cb.unpack()
 
+    def set_validation(self, y_test, weights_test=1):
+        """Attach held-out outcomes at the current test sites (mk_session_set_validation): y_test
+        (q*n_test, location-major like x_test) successes of weights_test trials (1: binary; 0 marks a
+        column that was not observed).  Needs test sites and x_test.  scores() then gives the log score,
+        Brier score and error rate per subset; a tiled session scores each tile from the replay that
+        makes its grids (outputs(), tile_grids()).  y_test=None detaches; so does set_test_sites."""
+        if y_test is None:
+            check(self._lib.mk_session_set_validation(self._h, None))
+            return
+        _y, _wt, v = validation_arrays(y_test, weights_test, self.q * self.n_test)
+        check(self._lib.mk_session_set_validation(self._h, ctypes.byref(v)))      # copied to HBM
+
+    def scores(self, pointwise=False):
+        """Held-out scores per subset after the run (mk_session_scores; the definitions are in
+        include/mk.h): {'subsets': (S, 5), 'names': the rows -- n (columns with trials), lpd (the log
+        predictive density of the held-out outcomes, binomial coefficient dropped), brier, err (share of
+        held-out trials the rule pmean >= 0.5 gets wrong), lconst (what full-likelihood log scores add)};
+        pointwise=True adds 'pointwise', per subset (q n_test) x 2: the posterior predictive mean
+        pmean_c of p(y = 1) and lpd_c.  A tiled session must have replayed every tile since
+        set_validation (MkError naming the first missing tile otherwise)."""
+        sb = ScoreBuffers(self.S, self.q * self.n_test, pointwise=pointwise)
+        check(self._lib.mk_session_scores(self._h, ctypes.byref(sb.c)))
+        return sb.unpack()
+
     def set_lookahead(self, mode):
         """Launch schedule before the first run: True / 1 lookahead (the next iteration's phi
         candidates factored while this iteration's inverse and sweep run), False / 0 sequential,
@@ -433,6 +458,27 @@ def chain_diagnostics(x, axis=0, device=0):
     out = np.zeros((C, _lib.N_DIAG))
     check(lib.mk_chain_diagnostics(dptr(chains), int(n), int(C), dptr(out), int(device)))
     return out.T.copy()
+
+
+def score_grid(p, y, weights=1, pointwise=False, device=0):
+    """Held-out scores of a grid of probabilities on the device (mk_score_grid; the kernels the sessions
+    use): p is n_rows x C, its rows equally weighted states of p(y = 1) per test column -- the combined
+    200-level grid result3, say; y (C) successes of weights trials.  Returns the row by name (n, lpd,
+    brier, err, lconst) and, with pointwise, 'pointwise' (C x 2: pmean_c, lpd_c)."""
+    lib = _lib.load()
+    p = np.asarray(p, dtype=np.float64)
+    if p.ndim != 2:
+        raise ValueError("error: score_grid takes a 2-d array (states x columns)")
+    n, C = p.shape
+    cols = _f64(p.T)                                          # one contiguous column of states per row
+    yv, wt, _v = validation_arrays(y, weights, C)
+    pw = np.zeros((2, C)) if pointwise else None
+    row = np.zeros(_lib.N_SCORE)
+    check(lib.mk_score_grid(dptr(cols), int(n), int(C), dptr(yv), dptr(wt), dptr(pw), dptr(row), int(device)))
+    out = dict(zip(_lib.SCORE_NAMES, row.tolist()))
+    if pointwise:
+        out["pointwise"] = pw.T.copy()
+    return out
 
 
 def correlation_batched(coords, phi, nu=None, cov_model="exponential", device=0):

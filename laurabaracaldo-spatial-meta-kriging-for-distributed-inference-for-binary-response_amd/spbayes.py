@@ -166,6 +166,39 @@ def spDiag(sp_obj, start=1, end=None, thin=1):
     return {"DIC": {k: row[k] for k in c["names"][:4]}, "WAIC": {k: row[k] for k in c["names"][4:]}}
 
 
+def spValidate(sp_obj, pred_coords, pred_covars, y, weights=1, start=1, end=None):
+    """Held-out validation of an spMvGLM fit, on the device: y ((q n_test), location-major like
+    pred_covars' rows) successes of `weights` trials observed at pred_coords are scored against the
+    posterior predictive of iterations start..end (1-based, inclusive), kriged from the recorded chain
+    in one replay.  Returns the row by name -- "n", "lpd" (log predictive density), "brier", "err"
+    (error rate of the rule pmean >= 0.5), "lconst" -- plus "pmean" (the posterior predictive mean of
+    p(y = 1) per test column) and "lpd.pointwise".  The definitions are in include/mk.h."""
+    ses = sp_obj.get("_session")
+    if ses is None:
+        raise ValueError("error: the spMvGLM fit was closed; spValidate needs its recorded chain states")
+    n_samples = sp_obj["_n_samples"]
+    end = n_samples if end is None else int(end)
+    start = int(start)
+    if not (1 <= start <= end <= n_samples):
+        raise ValueError("error: invalid start/end")
+    ct = np.asarray(pred_coords, float).reshape(-1, 2)
+    xt = np.asarray(pred_covars, float)
+    if xt.ndim != 2 or xt.shape[0] != ses.q * ct.shape[0]:
+        raise ValueError("error: pred.covars must have one row per prediction site and outcome (q * n rows)")
+    ses.set_test_sites(ct, x_test=pred_covars)
+    ses.set_kept_window(start, end)
+    ses.set_validation(y, weights)
+    try:
+        ses.outputs(quantiles=False, w_predict_sum=True)      # the one replay of the window
+        sc = ses.scores(pointwise=True)
+    finally:
+        ses.set_validation(None)
+    res = dict(zip(sc["names"], sc["subsets"][0].tolist()))
+    res["pmean"] = sc["pointwise"][0][:, 0].copy()
+    res["lpd.pointwise"] = sc["pointwise"][0][:, 1].copy()
+    return res
+
+
 def spPredict(sp_obj, pred_coords, pred_covars=None, start=1, end=None, thin=1, diagnostics=False):
     """p.w.predictive.samples ((q n_test) x kept) for kept iterations start..end (1-based,
     inclusive; every thin-th), kriged from the chain states spMvGLM recorded (no refit).

@@ -68,6 +68,10 @@ def main():
                     help="model assessment (DIC and WAIC, accumulated on the device over the kept iterations): one "
                          "more JSON line, {\"criteria\": the rows summed over the subsets}; one process (plain or "
                          "--devices)")
+    ap.add_argument("--validate", action="store_true",
+                    help="held-out validation against y.test (log score, Brier score, error rate on the device): "
+                         "one more JSON line, {\"validation\": the combined p grid's row, the median subset's row, "
+                         "AUC}; several ranks: rank 0 scores the combined grid, per-subset rows are left out")
     a = ap.parse_args()
     c = dict(CONFIGS[a.config])
     for k_arg, k_cfg in [("n", "n"), ("subsets", "K"), ("n_test", "n_test"), ("n_batch", "n_batch"),
@@ -116,8 +120,10 @@ def main():
     if subs:
         # one process, fused kriging: x.test goes in as MK.R:87 passes it, p.predict comes out
         ses = mk.Session(subs, cfg, coords_test=d["coords_test"], subset_base=lo, device=local,
-                         x_test=d["x_test"] if (world == 1 and not big) else None,            # MK.R:108
+                         x_test=d["x_test"] if ((world == 1 and not big) or a.validate) else None,   # MK.R:108
                          criteria=a.criteria)
+        if a.validate and world == 1:             # scored per subset: now (fused) or by the tile replays
+            ses.set_validation(d["y_test"])
         for b in range(cfg.n_batch):          # progress every n.report = 10 batches (MK.R:84)
             ses.run(cfg.batch_length)
             if rank == 0 and (b + 1) % 10 == 0:
@@ -127,13 +133,15 @@ def main():
         # one process: the grids to the host for the combine; N > 1: they stay in HBM (shard_grids below)
         # --diagnostics: with the grids when the kriging is fused; tiled: the parameters now, the draws tile by tile
         dg = ("parameters" if big else True) if a.diagnostics else False
-        out = (ses.outputs(quantiles=True, w_predict=not big, diagnostics=dg) if world == 1
+        out = (ses.outputs(quantiles=True, w_predict=not big, p_predict=False if big else None, diagnostics=dg)
+               if world == 1
                else {"parameters": [], "w_predict": []})
         crit = ses.criteria() if a.criteria else None
+        scores = ses.scores() if (a.validate and world == 1 and not big) else None
     else:                                         # K < world: this rank has no subsets, it joins the exchange
         t3 = time.perf_counter()
         out = {"parameters": [], "w_predict": []}
-        crit = None
+        crit = scores = None
     t["fit_s"] = t3 - t2
     t["predict_quantiles_s"] = time.perf_counter() - t3
     diag = {k: v for k, v in out.items() if "_diag" in k}
@@ -166,11 +174,19 @@ def main():
                                  f"limits differ); pass --predict-tile {int(tl[0])} or less")
         if not big:
             result2 = dmod.combine_sharded(shard_grids(1, C), K, dist, method=a.combine, device=dev, gpu=local)
+            if a.validate:
+                result3 = dmod.combine_sharded(shard_grids(2, C), K, dist, method=a.combine, device=dev, gpu=local)
         else:
             # tiled kriging (cfg5): per test-site tile, the column-sharded exchange + combine of that
             # tile's grids (sequential mean, or the Weiszfeld median per column)
             result2 = dmod.combine_tiles(tile_grids, c["n_test"], tile, q, K, dist, method=a.combine, device=dev,
                                          gpu=local)
+            if a.validate:      # the p grids of every tile: a second replay (the exchange takes one kind at a time)
+                def tile_grids_p(t0):
+                    tc = min(tile, c["n_test"] - t0)
+                    return ses.tile_grids(t0, prob=True)[1] if ses is not None else np.zeros((0, 200, q * tc))
+                result3 = dmod.combine_tiles(tile_grids_p, c["n_test"], tile, q, K, dist, method=a.combine, device=dev,
+                                             gpu=local)
     elif not big:
         obj = [{"parameters": out["parameters"][i], "w.predict": out["w_predict"][i]} for i in range(len(subs))]
         result, result2 = mk.combine_results(obj, device=local, method=a.combine)             # MK.R:123-133
@@ -181,12 +197,19 @@ def main():
         result = mk.combine_results([{"parameters": g} for g in out["parameters"]], device=local,
                                     method=a.combine)[0]
         result2 = np.zeros((200, C))
+        if a.validate:
+            result3 = np.zeros((200, C))
         if a.diagnostics:    # the worst rows over the subsets, filled tile by tile from each tile's own replay
             diag["w_predict_diag_worst"] = np.zeros((3, C))
         for t0 in range(0, c["n_test"], tile):
-            if a.diagnostics:
-                g, dt = ses.tile_grids(t0, diagnostics=True)
-                diag["w_predict_diag_worst"][:, t0 * q:t0 * q + g.shape[2]] = dt["w_predict_diag_worst"]
+            if a.diagnostics or a.validate:     # one replay: the grids, the tile's diagnostics and its scores
+                res = ses.tile_grids(t0, prob=a.validate, diagnostics=a.diagnostics)
+                g = res[0] if isinstance(res, tuple) else res
+                if a.diagnostics:
+                    diag["w_predict_diag_worst"][:, t0 * q:t0 * q + g.shape[2]] = res[-1]["w_predict_diag_worst"]
+                if a.validate:
+                    result3[:, t0 * q:t0 * q + g.shape[2]] = mk.combine_results(
+                        [{"parameters": x} for x in res[1]], device=local, method=a.combine)[0]
             else:
                 g = tile_grids(t0)
             result2[:, t0 * q:t0 * q + g.shape[2]] = mk.combine_results([{"parameters": x} for x in g], device=local,
@@ -194,6 +217,8 @@ def main():
             del g
             print(f"tile {t0 // tile + 1}/{(c['n_test'] + tile - 1) // tile}  {time.perf_counter() - t4:.1f}s",
                   file=sys.stderr, flush=True)
+    if a.validate and world == 1 and big:
+        scores = ses.scores()                     # every tile has been replayed
     if ses is not None:
         ses.close()
     t["combine_s"] = time.perf_counter() - t4
@@ -220,6 +245,8 @@ def main():
             print(json.dumps({"diagnostics": mk.convergence_report(diag)}), flush=True)
         if a.criteria:
             print(json.dumps({"criteria": dict(zip(crit["names"], crit["total"].tolist()))}), flush=True)
+        if a.validate and result3 is not None:
+            print(json.dumps({"validation": validation_line(mk, result3, d, scores, local)}), flush=True)
     if dist is not None:
         dist.destroy_process_group()
 
@@ -234,6 +261,17 @@ def predictive_scores(result3, d):
     p_true = 1.0 / (1.0 + np.exp(-(d["x_test"] @ d["beta_true"] + d["w_test_true"])))
     return {"p_test_brier": float(np.mean((med - d["y_test"]) ** 2)),
             "p_test_coverage_95": float(np.mean((p_true >= lo) & (p_true <= hi)))}
+
+
+def validation_line(mk, result3, d, scores, device):
+    """The combined p grid's held-out row (score_grid on the device), AUC of its pmean, and -- where the
+    per-subset rows exist -- the median subset's row."""
+    comb = mk.score_grid(np.asarray(result3), d["y_test"], pointwise=True, device=device)
+    rep = mk.validation_report(comb.pop("pointwise")[:, 0], d["y_test"])
+    line = {"combined": comb, "auc": rep["auc"]}
+    if scores is not None:
+        line["median_subset"] = mk.metakriging.median_subset_row(scores)
+    return line
 
 
 def node_main(a, c):
@@ -255,7 +293,7 @@ def node_main(a, c):
         d, K, q, cov_model=c["cov"], n_batch=c["n_batch"], batch_length=c["batch_length"], seed=a.seed,
         devices=devices, method=a.combine, predict_tile=c.get("predict_tile", 0), partition_method=a.partition,
         progress=progress, predictive=True,     # MK.R:87's x.test: the grids of p(y = 1) and result3
-        diagnostics=a.diagnostics, criteria=a.criteria)
+        diagnostics=a.diagnostics, criteria=a.criteria, validate=a.validate)
     ph["data_s"] = data_s
     rec = dict(config=a.config, workload=c, devices=devices, combine=a.combine, phases=ph,
                subset_iters_per_s=K * cfg.n_samples / ph["chains_s"])
@@ -271,6 +309,10 @@ def node_main(a, c):
         print(json.dumps({"diagnostics": mk.convergence_report(summ["diagnostics"])}), flush=True)
     if a.criteria:
         print(json.dumps({"criteria": summ["criteria"]}), flush=True)
+    if a.validate:
+        v = summ["validation"]
+        print(json.dumps({"validation": {"combined": v["combined"], "median_subset": v["median_subset"],
+                                         "auc": v["report"]["auc"]}}), flush=True)
 
 
 if __name__ == "__main__":
