@@ -154,8 +154,8 @@ int mk_session_outputs(mk_session* s, mk_outputs* out);
 int mk_session_set_test_sites(mk_session* s, int32_t n_test, const double* coords_test);
 /* Covariates of the session's current test sites: x_test (q*n_test) x p column-major (spPredict's
  * pred.covars), copied to HBM; the p_* outputs and the p grids need them.  mk_session_set_test_sites
- * drops them (new sites need their own), and held-out data attached by mk_session_set_validation with
- * them.  MK_E_ARG when the session has no test sites. */
+ * drops them (new sites need their own), and held-out data attached by mk_session_set_validation and
+ * maps asked for by mk_session_set_maps with them.  MK_E_ARG when the session has no test sites. */
 int mk_session_set_test_covars(mk_session* s, const double* x_test);
 int mk_session_set_kept_window(mk_session* s, int32_t first, int32_t last);
 /* After all iterations: the shard's 200-level grids, [n_subsets] x (200 x C) column-major -- which 0:
@@ -193,7 +193,8 @@ int mk_session_tile_grids_wp(mk_session* s, int32_t t0, double* out_w, double* o
  * model-assessment launches k_crit_accum / k_crit_replay / k_crit_finish / k_crit_total -- launches and
  * ms, always timed, 0 launches unless criteria were asked for; 16 the held-out scoring launches
  * k_score_cols / k_score_finish -- launches and ms, always timed, 0 launches unless validation data were
- * attached).  Flops are algorithmic, not executed: GEMM tiles 2 m n k, the diagonal tile's
+ * attached; 17 the posterior-map launches k_map_cols -- launches and ms, always timed, 0 launches unless
+ * maps were asked for).  Flops are algorithmic, not executed: GEMM tiles 2 m n k, the diagonal tile's
  * update as a SYRK, solves and inverse products over their triangles.  mk_session_profile(s, enable)
  * before mk_session_run: enable 0 = off, 1 = every kind, otherwise a mask with bit (1 + kind) per kind
  * bracketed (e.g. 2 << 0 = the panel update only; fewer events, less overhead). */
@@ -409,6 +410,67 @@ int mk_score_grid(const double* p, int32_t n_rows, int64_t n_cols, const double*
 int mk_meta_fit_val(const mk_problem* prob, const mk_config* cfg, const int32_t* devices, int32_t n_devices,
                     mk_progress_fn progress, void* user, mk_outputs* out, mk_combined* comb, mk_diagnostics* diag,
                     mk_criteria* crit, const mk_validation* val, mk_scores* scores);
+
+/* ---- posterior maps: mean, sd and exceedance probabilities of p(y = 1) at the test sites ----
+ * The map a binary spatial model is drawn as: per test column the posterior mean and standard deviation
+ * of the latent w and of p(y = 1), and the posterior probability that p exceeds each of J policy
+ * thresholds ("prevalence above 20 %").  Thresholds u_1..u_J are on the probability scale,
+ * 0 <= J <= MK_MAP_MAXT, every u_j finite.
+ * Each subset on its own; k = 1..n the kept states of the window in time order, c a test column (site x
+ * outcome, location-major like x_test):
+ *   eta_kc, p_kc  exactly pred_eta and pred_linkinv: p is the p of p_pred_samples bit for bit, as in the
+ *                 held-out scores
+ *   mean of v (v = w or p)  (sum_k v_k) / n, summed in time order from zero: pmean's own expression --
+ *                 with validation data attached the p_mean plane equals the scores' pmean bit for bit
+ *   sd of v       Welford's recurrence in time order: m = 0, M2 = 0; per state d = v - m, m = m + d/k,
+ *                 M2 = M2 + d (v - m); sd = sqrt(M2 / (n - 1)), NaN when n = 1.  Plain operations, no
+ *                 contraction
+ *   exc_j         #{k : p_kc > u_j} / n; the inequality is strict
+ * A non-finite draw or eta makes every plane of that column NaN.
+ * Planes per subset: MK_N_MAP_BASE + J, in the order w_mean, w_sd, p_mean, p_sd, exc_1..exc_J; output
+ * per subset (q*n_test) x (4 + J) column-major.  One thread owns one column and walks its states
+ * serially, so nothing in a column depends on the tile, the stream group, the workgroup or the device
+ * block it ran in.
+ * The combined posterior is a grid of levels; as with mk_score_grid its n_rows levels are equally
+ * weighted states, read and not computed: mk_map_grid gives n_cols x (2 + J): mean, sd, exc_1..J of the
+ * grid it is handed, and the node call fills the combined planes in the 4 + J order -- w_mean and w_sd
+ * from comb->result2; p_mean, p_sd and exc from comb->result3 -- for the mean combine and the Weiszfeld
+ * median alike. */
+#define MK_MAP_MAXT 8     /* thresholds at most */
+#define MK_N_MAP_BASE 4   /* planes before the exceedances: w_mean, w_sd, p_mean, p_sd */
+typedef struct mk_map_spec { const double* thresholds; int32_t n_thresholds; } mk_map_spec;
+typedef struct mk_maps {              /* caller-allocated, either pointer may be NULL */
+  double* subsets;             /* [n_subsets] x ((q*n_test) x (4 + J)) */
+  double* combined;            /* (q*n_test) x (4 + J): the combined grids' planes (node call only) */
+} mk_maps;
+/* Ask the session for the maps of its current test sites (NULL detaches and frees).  Needs test sites,
+ * x_test and recorded samples, else MK_E_ARG; the thresholds are checked before any device is touched: a
+ * non-finite value or n_thresholds outside 0 .. MK_MAP_MAXT is MK_E_ARG naming the index.  A tiled
+ * session takes its plane buffer here and only here: 8 (4 + J) bytes per (subset, test column);
+ * MK_E_NOMEM names the remedies.  While attached, every tile replay of a tiled session --
+ * mk_session_outputs, mk_session_tile_grids, mk_session_tile_grids_wp -- also fills that tile's columns
+ * of the planes, from the same replay and over its kept window.  mk_session_set_test_sites detaches.
+ * Nothing is launched or allocated for the maps unless they were asked for. */
+int mk_session_set_maps(mk_session* s, const mk_map_spec* spec);
+/* After all iterations.  A fused session makes the planes from its kriging draws (all kept states) now,
+ * in scratch held for the call.  A tiled session copies its buffer out: MK_E_ARG, naming the first such
+ * tile, if some tile has not been replayed over the current kept window since the maps were attached.
+ * combined is not written here. */
+int mk_session_maps(mk_session* s, mk_maps* out);
+/* mean, sd and exceedances of a grid on the host: grid is n_rows x n_cols column-major (e.g.
+ * comb->result3 with n_rows = 200), out n_cols x (2 + n_thresholds) column-major.  Columns are uploaded
+ * in chunks (bounded in bytes; MK_MAP_CHUNK=<columns> overrides); a column is one thread's work, so
+ * nothing depends on the chunk. */
+int mk_map_grid(const double* grid, int32_t n_rows, int64_t n_cols, const double* thresholds, int32_t n_thresholds,
+                double* out, int32_t device);
+/* mk_meta_fit_val with posterior maps (mk_meta_fit_val is this call with two NULLs): every block
+ * attaches the spec and writes its subsets' planes at their global offsets; maps->combined comes from
+ * mk_map_grid on the host copies of comb->result2 and comb->result3 (MK_E_ARG when either is not asked
+ * for).  Nothing is added to the exchange. */
+int mk_meta_fit_maps(const mk_problem* prob, const mk_config* cfg, const int32_t* devices, int32_t n_devices,
+                     mk_progress_fn progress, void* user, mk_outputs* out, mk_combined* comb, mk_diagnostics* diag,
+                     mk_criteria* crit, const mk_validation* val, mk_scores* scores, const mk_map_spec* spec,
+                     mk_maps* maps);
 
 /* ---- combine (MK.R:123-133): out = (grid_1 + ... + grid_K) / K, sequential order ---- */
 int mk_combine(const double* grids, int32_t K, int64_t grid_len, double* out, int32_t device);

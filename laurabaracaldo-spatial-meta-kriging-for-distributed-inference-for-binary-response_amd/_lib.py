@@ -29,6 +29,9 @@ N_CRIT = 8             # MK_N_CRIT: the rows of mk_criteria, in CRIT_NAMES' orde
 CRIT_NAMES = ["bar.D", "D.bar.Omega", "pD", "DIC", "lppd", "p.waic", "WAIC", "lconst"]
 N_SCORE = 5            # MK_N_SCORE: the rows of mk_scores, in SCORE_NAMES' order
 SCORE_NAMES = ["n", "lpd", "brier", "err", "lconst"]
+MAP_MAXT = 8           # MK_MAP_MAXT: exceedance thresholds at most
+N_MAP_BASE = 4         # MK_N_MAP_BASE: the planes before the exceedances, in MAP_BASE_NAMES' order
+MAP_BASE_NAMES = ["w_mean", "w_sd", "p_mean", "p_sd"]
 
 _dp = ctypes.POINTER(ctypes.c_double)
 _ip = ctypes.POINTER(ctypes.c_int32)
@@ -93,6 +96,14 @@ class Scores(ctypes.Structure):
     _fields_ = [("subsets", _dp), ("pointwise", _dp), ("combined", _dp), ("combined_pointwise", _dp)]
 
 
+class MapSpec(ctypes.Structure):
+    _fields_ = [("thresholds", _dp), ("n_thresholds", ctypes.c_int32)]
+
+
+class Maps(ctypes.Structure):
+    _fields_ = [("subsets", _dp), ("combined", _dp)]
+
+
 # int (*mk_progress_fn)(void* user, int32_t iterations, int32_t n_samples)
 PROGRESS_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32)
 
@@ -104,6 +115,13 @@ EXPORTS = {
                                        PROGRESS_FN, ctypes.c_void_p, ctypes.POINTER(Outputs), ctypes.POINTER(Combined),
                                        ctypes.POINTER(Diagnostics), ctypes.POINTER(Criteria), ctypes.POINTER(Validation),
                                        ctypes.POINTER(Scores)]),
+    "mk_meta_fit_maps": (ctypes.c_int, [ctypes.POINTER(Problem), ctypes.POINTER(Config), _ip, ctypes.c_int32,
+                                        PROGRESS_FN, ctypes.c_void_p, ctypes.POINTER(Outputs), ctypes.POINTER(Combined),
+                                        ctypes.POINTER(Diagnostics), ctypes.POINTER(Criteria), ctypes.POINTER(Validation),
+                                        ctypes.POINTER(Scores), ctypes.POINTER(MapSpec), ctypes.POINTER(Maps)]),
+    "mk_session_set_maps": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(MapSpec)]),
+    "mk_session_maps": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(Maps)]),
+    "mk_map_grid": (ctypes.c_int, [_dp, ctypes.c_int32, ctypes.c_int64, _dp, ctypes.c_int32, _dp, ctypes.c_int32]),
     "mk_session_set_validation": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(Validation)]),
     "mk_session_scores": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(Scores)]),
     "mk_score_grid": (ctypes.c_int, [_dp, ctypes.c_int32, ctypes.c_int64, _dp, _dp, _dp, _dp, ctypes.c_int32]),

@@ -21,6 +21,9 @@ int session_grids(mk_session* s, GridKind kind, double* d_out);   // into HBM; r
 int session_tile_grids(mk_session* s, int t0, double* d_out, mk_outputs* o, double* d_out_p = nullptr);
 // A plain non-blocking stream of the current device from libmk's stream pool, and its return
 // (drained by the caller): the node driver's per-block streams live as long as the sessions' do.
+// mk_maps.hip: MK_E_ARG naming the index of a non-finite threshold, or J when it is outside 0 .. MK_MAP_MAXT;
+// touches no device.
+int map_spec_check(const double* thresholds, int J);
 hipError_t stream_acquire(int device, hipStream_t* st);
 void stream_release(int device, hipStream_t st);
 

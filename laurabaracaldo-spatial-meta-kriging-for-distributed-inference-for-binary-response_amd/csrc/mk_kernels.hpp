@@ -135,6 +135,10 @@ template <bool GRID>
 __global__ void k_score_cols(const double* data, long subset_stride, long row_stride, long col_stride, int n, int n_cols,
                              ProbSrc ps, const double* y, const double* wt, long col0, long C, double* pw);
 __global__ void k_score_finish(const double* pw, const double* y, const double* wt, long C, double* rows);
+// mk_maps.hip
+template <bool GRID>
+__global__ void k_map_cols(const double* data, long subset_stride, long row_stride, long col_stride, int n, int n_cols,
+                           ProbSrc ps, MapThr th, long col0, long C, double* planes);
 // mk_post.hip
 __global__ void k_weiszfeld(const double* grids, int K, int L, long C, int max_iter, double tol, double* out, int* iters);
 __global__ void k_post_index(uint64_t seed, int samplesize, int n_levels, int* idx);

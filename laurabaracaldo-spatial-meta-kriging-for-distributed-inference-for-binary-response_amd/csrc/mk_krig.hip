@@ -114,6 +114,7 @@ extern "C" int mk_session_set_test_sites(mk_session* s, int32_t n_test, const do
   s->diag_on = false;                      // a diagnostics sink was sized for the sites that go
   s->diag_sink = mk_diagnostics{};
   validation_detach(s);                    // held-out data belonged to the sites that go
+  maps_detach(s);                          // and the maps' planes were sized for them
   int rc = set_test_covars(s, nullptr);   // the covariates belonged to the sites that go
   if (rc) return rc;
   return kriging_buffers(s, n_test, coords_test);
@@ -226,6 +227,11 @@ static int tile_outputs(mk_session* s, int t0, double* dq, double* dqp, mk_outpu
   // attached validation data: this tile's columns of the held-out scores, from the same draws
   if (s->val.on) {
     const int rc = tile_scores(s, t0, n_kept, Ct);
+    if (rc) return rc;
+  }
+  // maps asked for: this tile's columns of the planes, from the same draws
+  if (s->maps.on) {
+    const int rc = tile_maps(s, t0, n_kept, Ct);
     if (rc) return rc;
   }
   HIPCHK(hipStreamSynchronize(st));

@@ -409,6 +409,13 @@ extern "C" int mk_meta_fit_ex(const mk_problem* pr, const mk_config* c, const in
 extern "C" int mk_meta_fit_val(const mk_problem* pr, const mk_config* c, const int32_t* devices, int32_t G,
                                mk_progress_fn progress, void* user, mk_outputs* out, mk_combined* comb,
                                mk_diagnostics* diag, mk_criteria* crit, const mk_validation* val, mk_scores* scores) {
+  return mk_meta_fit_maps(pr, c, devices, G, progress, user, out, comb, diag, crit, val, scores, nullptr, nullptr);
+}
+
+extern "C" int mk_meta_fit_maps(const mk_problem* pr, const mk_config* c, const int32_t* devices, int32_t G,
+                                mk_progress_fn progress, void* user, mk_outputs* out, mk_combined* comb,
+                                mk_diagnostics* diag, mk_criteria* crit, const mk_validation* val, mk_scores* scores,
+                                const mk_map_spec* spec, mk_maps* maps) {
   if (!pr || !c) return fail(MK_E_ARG, "null problem/config");
   if (!devices || G < 1) return fail(MK_E_ARG, "n_devices must be >= 1 with a device list");
   const int K = pr->n_subsets;
@@ -416,6 +423,15 @@ extern "C" int mk_meta_fit_val(const mk_problem* pr, const mk_config* c, const i
   if (pr->q < 1 || pr->q > 4 || pr->p < 1 || !pr->n_part) return fail(MK_E_ARG, "bad q / p / n_part");
   if (comb && comb->method != MK_COMBINE_MEAN && comb->method != MK_COMBINE_MEDIAN)
     return fail(MK_E_ARG, "combine method must be MK_COMBINE_MEAN or MK_COMBINE_MEDIAN");
+  const bool mp_comb = maps && maps->combined;
+  const bool mp_sub = maps && maps->subsets;
+  int J = 0;
+  if (mp_comb || mp_sub) {   // the thresholds, before any device is touched
+    if (!spec) return fail(MK_E_ARG, "posterior maps need a map spec");
+    const int e = map_spec_check(spec->thresholds, spec->n_thresholds);
+    if (e) return e;
+    J = spec->n_thresholds;
+  }
   ApiCall call(__func__);
   DeviceGuard dg;   // the caller's current device is restored on every return path
   int ndev = 0;
@@ -438,6 +454,10 @@ extern "C" int mk_meta_fit_val(const mk_problem* pr, const mk_config* c, const i
   if (want_val && (!pr->x_test || pr->n_test < 1)) return fail(MK_E_ARG, "held-out scores need test sites and x_test");
   if (sc_comb && !(comb && comb->result3))
     return fail(MK_E_ARG, "the combined grid's scores are those of comb->result3: ask for it");
+  if ((mp_comb || mp_sub) && (!pr->x_test || pr->n_test < 1))
+    return fail(MK_E_ARG, "posterior maps need test sites and x_test");
+  if (mp_comb && !(comb && comb->result2 && comb->result3))
+    return fail(MK_E_ARG, "the combined maps are those of comb->result2 (w) and comb->result3 (p): ask for both");
   const int q = pr->q, p = pr->p, n_samples = c->n_batch * c->batch_length;
   if (c->n_batch < 1 || c->batch_length < 1) return fail(MK_E_ARG, "n.batch and batch.length must be >= 1");
 
@@ -482,7 +502,8 @@ extern "C" int mk_meta_fit_val(const mk_problem* pr, const mk_config* c, const i
     sc.device = x.dev;
     int e = mk_session_create(&sp, &sc, &x.ses);
     if (e || (want_crit && (e = mk_session_set_criteria(x.ses, 1)))) return e;
-    return sc_sub ? mk_session_set_validation(x.ses, val) : 0;
+    if (sc_sub && (e = mk_session_set_validation(x.ses, val))) return e;
+    return mp_sub ? mk_session_set_maps(x.ses, spec) : 0;
   });
   if (rc) return rc;
   if (nd.use_rccl) {
@@ -642,7 +663,7 @@ extern "C" int mk_meta_fit_val(const mk_problem* pr, const mk_config* c, const i
     const PredKind pk{GRID_P, out ? out->p_predict : nullptr, out ? out->p_predict_sum : nullptr,
                       comb ? comb->result3 : nullptr, &Block::grids_p};
     const bool draws = out && (out->w_pred_samples || out->p_pred_samples);
-    const bool replay = tiled && (w.asked() || pk.asked() || draws || dg_w || dg_p || sc_sub);   // one replay per tile serves them all
+    const bool replay = tiled && (w.asked() || pk.asked() || draws || dg_w || dg_p || sc_sub || mp_sub);   // one replay per tile serves them all
     if (!tiled) {
       for (const PredKind* k : {&pk, &w})   // p before w
         if (k->asked() && (rc = whole_grids(k->kind, C, k->h_each, k->h_comb, k->h_sum))) return rc;
@@ -697,6 +718,22 @@ extern "C" int mk_meta_fit_val(const mk_problem* pr, const mk_config* c, const i
   }
   if (sc_comb && (rc = mk_score_grid(comb->result3, L, C, val->y_test, val->wt_test, scores->combined_pointwise,
                                      scores->combined, devices[0])))
+    return rc;
+  // ---- posterior maps (optional): the blocks' planes at their global offsets, as with the scores; the
+  // combined planes from the host copies of the two combined grids: w_mean, w_sd of result2, then
+  // p_mean, p_sd, exc_1..J of result3
+  if (mp_sub && n_test > 0) {
+    rc = nd.pool->run([&](int r) -> int {
+      Block& x = *nd.b[r];
+      if (!x.ses) return 0;
+      mk_maps m{};
+      m.subsets = maps->subsets + (size_t)x.lo * (MK_N_MAP_BASE + J) * C;
+      return mk_session_maps(x.ses, &m);
+    });
+    if (rc) return rc;
+  }
+  if (mp_comb && ((rc = mk_map_grid(comb->result2, L, C, nullptr, 0, maps->combined, devices[0])) ||
+                  (rc = mk_map_grid(comb->result3, L, C, spec->thresholds, J, maps->combined + 2 * (size_t)C, devices[0]))))
     return rc;
   if (diag) {   // the worst rows over all K: the blocks' own, folded here
     bool first = true;

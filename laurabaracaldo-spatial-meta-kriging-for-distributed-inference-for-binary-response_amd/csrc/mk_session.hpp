@@ -9,6 +9,7 @@
 //   mk_diag.hip      chain diagnostics: the launcher, the session entry points, the tile sink
 //   mk_criteria.hip  model assessment (DIC, WAIC): the kernels, the scratch, the session entry points
 //   mk_scores.hip    held-out validation (log score, Brier, error rate): the kernels, the entry points
+//   mk_maps.hip      posterior maps (mean, sd, exceedance of p(y = 1)): the kernel, the entry points
 //
 // mk_internal.hpp stays the interface towards mk_multi.hip and mk_watch.hip.
 #pragma once
@@ -49,7 +50,7 @@ static inline int env_int(const char* name, int dflt) {
   return (v && *v) ? std::atoi(v) : dflt;
 }
 
-constexpr int NKSTAT = 17;
+constexpr int NKSTAT = 18;
 // KS_CHOL_UPDATE: the 128-tile panel-update launches (k_chol_update<128>); KS_CHOL_UPDATE_SUB:
 // the 64- / 32-sub-tile ones (small grids).  Together: the roofline kernel k_chol_update.
 // KS_UPDATE_BUSY: both, with the time of launches that overlap (the split schedule's bulk and
@@ -59,7 +60,7 @@ constexpr int NKSTAT = 17;
 // KS_COV: the candidates' covariance assembly (k_cov_candidate, with k_matern_table for Matern).
 enum { KS_CHOL_UPDATE = 0, KS_CHOL_DIAG, KS_CHOL_TRSM, KS_SWEEP, KS_LAUUM, KS_ITER, KS_INV, KS_CHOL_UPDATE_SUB,
        KS_UPDATE_BUSY, KS_PRED_VAR, KS_COV, KS_SWEEP_FALLBACK, KS_KRIG_CHEB, KS_KRIG_FALLBACK, KS_DIAG, KS_CRIT,
-       KS_SCORE };
+       KS_SCORE, KS_MAPS };
 // KS_KRIG_CHEB: tiles kriged by phi interpolation (predict_tile_cheb): launches = tiles, flops = exact
 // s evaluations ((subset, node or check point) pairs), total_ms = the largest check difference seen
 // (not a time).  KS_KRIG_FALLBACK: tiles whose check failed and were replayed exactly (launches), and
@@ -72,6 +73,9 @@ enum { KS_CHOL_UPDATE = 0, KS_CHOL_DIAG, KS_CHOL_TRSM, KS_SWEEP, KS_LAUUM, KS_IT
 // KS_SCORE: the held-out scoring launches (k_score_cols per tile replay or mk_session_scores, k_score_finish
 // per mk_session_scores), bracketed by events whether or not the profiler is on; none are made unless
 // validation data were attached.
+// KS_MAPS: the posterior-map launches (k_map_cols per tile replay of a tiled session, per mk_session_maps of
+// a fused one), bracketed by events whether or not the profiler is on; none are made unless maps were asked
+// for.
 // KS_SWEEP_FALLBACK: launches = (subset, iteration) sweeps k_sweep_mg refused admission and its
 // k_sweep fallback ran (counted on the device, read at the end of every mk_session_run; no timing).
 
@@ -241,6 +245,16 @@ struct Validation {
   int lo = -1, n = -1;        // the kept window those replays ran over
 };
 
+// mk_maps.hip.  Posterior maps (mk_session_set_maps): the thresholds and, for a tiled session, the
+// planes its tile replays fill (allocated when maps are asked for, never otherwise).
+struct Maps {
+  bool on = false;
+  MapThr th{};
+  double* planes = nullptr;   // tiled: [S][MK_N_MAP_BASE + J][q n_test_all]
+  std::vector<char> done;     // tiled: per tile, replayed since the maps were attached
+  int lo = -1, n = -1;        // the kept window those replays ran over
+};
+
 }  // namespace mk
 
 struct mk_session {
@@ -279,6 +293,7 @@ struct mk_session {
   mk::Profiler prof;
   mk::Criteria crit;
   mk::Validation val;
+  mk::Maps maps;
   mk_diagnostics diag_sink{};           // mk_session_set_diagnostics: filled by every tile replay while diag_on
   bool diag_on = false;
   hipError_t launch_err = hipSuccess;   // first failed kernel launch of a run
@@ -408,5 +423,15 @@ void crit_drain(mk_session* s, bool price);
 int tile_scores(mk_session* s, int t0, int n_kept, int Ct);
 // Frees the validation data and the pair buffer (mk_session_set_test_sites; NULL data).
 void validation_detach(mk_session* s);
+
+// ---- mk_maps.hip
+// The maps' share of tile [t0, ..): the planes of the draws in md.w_pred ([S][n_kept][Ct]) into the
+// session's plane buffer.  Timed as KS_MAPS; returns after the stream is idle.
+int tile_maps(mk_session* s, int t0, int n_kept, int Ct);
+// Frees the plane buffer and forgets the thresholds (mk_session_set_test_sites; a NULL spec).
+void maps_detach(mk_session* s);
+// thresholds[0 .. J) into th (the slots past J at +inf); MK_E_ARG naming the index of a non-finite value, or J
+// when it is outside 0 .. MK_MAP_MAXT.  Touches no device.
+int map_thresholds(const double* thresholds, int J, MapThr* th);
 
 }  // namespace mk

@@ -19,6 +19,7 @@
 // its pair from blockIdx and the cur[] slot table, so no host round trip is
 // needed between the steps of an iteration.
 #pragma once
+#include "../../include/mk.h"
 #include "mk_common.hpp"
 
 #define MK_QMAX 4
@@ -133,6 +134,14 @@ struct ProbSrc {
   long ldx;                // q * n_test_all
   long x_off;              // the first column's row of x (a tile's t0 * q; 0 when fused)
   int p, link;
+};
+
+// The exceedance thresholds of the posterior maps (mk_maps.hip), passed to k_map_cols by value: u[0 .. J)
+// as given, the slots past J at +inf (no probability exceeds them), so the kernel counts all
+// MK_MAP_MAXT in registers whatever J is.
+struct MapThr {
+  double u[MK_MAP_MAXT];
+  int J;
 };
 
 // Model-assessment scratch (mk_criteria.hip; include/mk.h "model assessment").  Per observation

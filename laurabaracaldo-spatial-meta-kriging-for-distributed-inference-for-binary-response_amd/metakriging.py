@@ -90,7 +90,7 @@ def r_sample_replace(n, size, seed):
 
 def meta_fit(y, x, weight, coords, q, index_part, coords_test=None, cfg=None, subset_base=0, device=0,
              cov_model="exponential", n_batch=100, batch_length=50, seed=20250114, x_test=None, diagnostics=False,
-             criteria=False, y_test=None, weights_test=1):
+             criteria=False, y_test=None, weights_test=1, maps=None):
     """All subsets of one shard on one GPU; returns the list `obj` of MK.R:108 for those subsets:
     [{'parameters': 200 x P, 'w.predict': 200 x (q n_test)}, ...]; with x_test (MK.R:87's x.test) each
     also holds 'p.predict' (200 x (q n_test)): the grid of p(y = 1) at the test sites.
@@ -99,7 +99,9 @@ def meta_fit(y, x, weight, coords, q, index_part, coords_test=None, cfg=None, su
     criteria=True: each also holds 'criteria', the subset's DIC and WAIC rows by name (bar.D, D.bar.Omega,
     pD, DIC, lppd, p.waic, WAIC, lconst; Session.criteria), accumulated in chain over its kept states.
     y_test (with weights_test trials; needs x_test): each also holds 'scores', the subset's held-out row by
-    name (n, lpd, brier, err, lconst; Session.scores) of its posterior predictive at the test sites."""
+    name (n, lpd, brier, err, lconst; Session.scores) of its posterior predictive at the test sites.
+    maps (exceedance thresholds, () for none; needs x_test): each also holds 'maps', the subset's (q n_test) x
+    (4 + J) planes, and 'maps.names' (w_mean, w_sd, p_mean, p_sd, exc_1..J; Session.maps)."""
     p = np.asarray(x).shape[1]
     if cfg is None:
         beta0, bt = start_values(y, x, weight, q)
@@ -110,10 +112,13 @@ def meta_fit(y, x, weight, coords, q, index_part, coords_test=None, cfg=None, su
                  criteria=criteria) as ses:
         if y_test is not None:
             ses.set_validation(y_test, weights_test)
+        if maps is not None:
+            ses.set_maps(maps)
         ses.run(cfg.n_samples)
         out = ses.outputs(diagnostics=diagnostics)
         crit = ses.criteria() if criteria else None
         scores = ses.scores() if y_test is not None else None
+        planes = ses.maps() if maps is not None else None
     res = []
     for i in range(len(subsets)):
         d = {"parameters": out["parameters"][i]}
@@ -128,6 +133,8 @@ def meta_fit(y, x, weight, coords, q, index_part, coords_test=None, cfg=None, su
             d["criteria"] = dict(zip(crit["names"], crit["subsets"][i].tolist()))
         if scores is not None:
             d["scores"] = dict(zip(scores["names"], scores["subsets"][i].tolist()))
+        if planes is not None:
+            d["maps"], d["maps.names"] = planes["subsets"][i], list(planes["names"])
         res.append(d)
     return res
 
@@ -262,7 +269,7 @@ def posterior_summary(result, result2, x_test, q=None, samplesize=1000, seed=202
 
 def reference_flow(d, K, q, cov_model="exponential", n_batch=100, batch_length=50, seed=20250114, devices=(0,),
                    method="mean", predict_tile=0, partition_method="R", samplesize=1000, progress=None,
-                   predictive=False, diagnostics=False, criteria=False, validate=False):
+                   predictive=False, diagnostics=False, criteria=False, validate=False, maps=None):
     """The reference script end to end in one process over the GPUs in `devices` (mk_meta_fit: the
     subsets sharded over them in-library, the combine device to device):
 
@@ -284,6 +291,9 @@ def reference_flow(d, K, q, cov_model="exponential", n_batch=100, batch_length=5
     holds 'combined' (the combined p grid's row by name), 'subsets' (K x 5), 'names', 'median_subset'
     (the row of the subset whose lpd is the median of the K) and 'report' (validation_report of the
     combined grid's pmean: AUC and the reliability table).
+    maps (exceedance thresholds, () for none; implies predictive): summary["maps"] holds 'names', 'thresholds'
+    and 'combined' ((q n_test) x (4 + J): the combined grids' mean, sd and exceedance planes, meta_fit_node's
+    'maps_combined') and 'subsets' (per subset the same planes of its own posterior).
     Returns (phases, result, result2, summary, cfg) -- phases in seconds of
     wall clock: set-up (partition, glm, subset slicing), the chains (to the last batch boundary),
     quantiles + combine, post-processing, and the whole."""
@@ -308,9 +318,10 @@ def reference_flow(d, K, q, cov_model="exponential", n_batch=100, batch_length=5
         return bool(progress(it, n_samples)) if progress is not None else False
 
     fit = meta_fit_node(subs, cfg, coords_test=d["coords_test"], devices=devices, method=method, per_subset=False,
-                        progress=_progress, x_test=d["x_test"] if predictive or validate else None,
+                        progress=_progress, x_test=d["x_test"] if predictive or validate or maps is not None else None,
                         diagnostics=diagnostics, criteria=criteria,
-                        validation=dict(y_test=d["y_test"], pointwise=True) if validate else None)   # MK.R:100-133
+                        validation=dict(y_test=d["y_test"], pointwise=True) if validate else None,
+                        maps=maps)                                                           # MK.R:100-133
     t3 = time.perf_counter()
     t["chains_s"] = stamp.get("chains", t3) - t1
     t["quantiles_combine_s"] = t3 - stamp.get("chains", t3)
@@ -324,6 +335,8 @@ def reference_flow(d, K, q, cov_model="exponential", n_batch=100, batch_length=5
         summ["diagnostics"] = {k: v for k, v in fit.items() if k.endswith("_diag_worst")}
     if criteria:
         summ["criteria"] = dict(zip(fit["criteria"]["names"], fit["criteria"]["total"].tolist()))
+    if maps is not None:
+        summ["maps"] = dict(fit["maps"], combined=fit["maps_combined"])
     if validate:
         sc = fit["scores"]
         summ["validation"] = dict(combined=sc["combined"], subsets=sc["subsets"], names=sc["names"],

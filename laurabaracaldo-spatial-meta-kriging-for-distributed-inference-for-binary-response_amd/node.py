@@ -15,7 +15,8 @@ import numpy as np
 
 from . import _lib
 from ._lib import Combined, check
-from .outbuf import CriteriaBuffers, DiagnosticBuffers, OutputBuffers, ScoreBuffers, validation_arrays
+from .outbuf import (CriteriaBuffers, DiagnosticBuffers, MapBuffers, OutputBuffers, ScoreBuffers, map_spec,
+                     validation_arrays)
 from .session import PackedProblem
 
 N_LEVELS = _lib.N_LEVELS
@@ -24,7 +25,7 @@ N_LEVELS = _lib.N_LEVELS
 def meta_fit_node(subsets, cfg, coords_test=None, devices=(0,), subset_base=0, method="mean", per_subset=True,
                   samples=False, w_samples=False, w_pred_samples=False, acceptance=False, w_predict_sum=False,
                   progress=None, record_w=False, max_iter=100, tol=1e-12, x_test=None, p_pred_samples=False,
-                  p_predict_sum=False, diagnostics=False, criteria=False, validation=None):
+                  p_predict_sum=False, diagnostics=False, criteria=False, validation=None, maps=None):
     """Fit all subsets over `devices` and combine.  Returns a dict with 'result' (200 x P, MK.R:127),
     'result2' (200 x q n_test, MK.R:133; None without test sites), 'exchange' ('rccl' / 'copy'),
     'comm_ranks' (the ranks the exchange spans: RCCL's own ncclCommCount, or the blocks for copies),
@@ -43,7 +44,11 @@ def meta_fit_node(subsets, cfg, coords_test=None, devices=(0,), subset_base=0, m
     a dict with 'y_test' and optionally 'weights_test' and 'pointwise' -- adds 'scores': Session.scores'
     dict for all K subsets ('subsets' K x 5: n, lpd, brier, err, lconst; 'names') plus 'combined', the row
     of the combined p grid result3 by name (score_grid's); with pointwise also the 'pointwise' pairs per
-    subset and 'combined_pointwise'.  Needs x_test."""
+    subset and 'combined_pointwise'.  Needs x_test.
+    maps (mk_meta_fit_maps): exceedance thresholds on the probability scale (() for none; None: no maps)
+    -- adds 'maps': Session.maps' dict for all K subsets ('names': w_mean, w_sd, p_mean, p_sd, exc_1..J;
+    'thresholds'; 'subsets': per subset C x (4 + J)) and 'maps_combined' (C x (4 + J)): the same planes of
+    the combined grids, w_mean and w_sd from result2, the others from result3 (map_grid's).  Needs x_test."""
     lib = _lib.load()
     if method not in ("mean", "median"):
         raise ValueError(f"error: unknown combine method '{method}'")
@@ -94,11 +99,19 @@ def meta_fit_node(subsets, cfg, coords_test=None, devices=(0,), subset_base=0, m
             vy, vw, vpw = validation, 1, False
         val = validation_arrays(vy, vw, C)
         sb = ScoreBuffers(K, C, pointwise=bool(vpw), combined=True)
-    check(lib.mk_meta_fit_val(ctypes.byref(pp.c), ctypes.byref(c), devs.ctypes.data_as(_lib._ip), len(devs), fn, None,
-                              ctypes.byref(ob.c), ctypes.byref(cb), ctypes.byref(db.c) if db is not None else None,
-                              ctypes.byref(kb.c) if kb is not None else None,
-                              ctypes.byref(val[2]) if val is not None else None,
-                              ctypes.byref(sb.c) if sb is not None else None))
+    mb = spec = None
+    if maps is not None:
+        if not have_x:
+            raise ValueError("error: maps need test sites and x_test")
+        spec = map_spec(maps)
+        mb = MapBuffers(K, C, spec[0].size, combined=True)
+    check(lib.mk_meta_fit_maps(ctypes.byref(pp.c), ctypes.byref(c), devs.ctypes.data_as(_lib._ip), len(devs), fn, None,
+                               ctypes.byref(ob.c), ctypes.byref(cb), ctypes.byref(db.c) if db is not None else None,
+                               ctypes.byref(kb.c) if kb is not None else None,
+                               ctypes.byref(val[2]) if val is not None else None,
+                               ctypes.byref(sb.c) if sb is not None else None,
+                               ctypes.byref(spec[1]) if spec is not None else None,
+                               ctypes.byref(mb.c) if mb is not None else None))
     del keep
     out = {"result": result.T.copy(), "result2": None if result2 is None else result2.T.copy(),
            "exchange": "rccl" if cb.exchange else "copy", "comm_ranks": int(cb.comm_ranks)}
@@ -111,4 +124,7 @@ def meta_fit_node(subsets, cfg, coords_test=None, devices=(0,), subset_base=0, m
         out["criteria"] = kb.unpack()
     if sb is not None:
         out["scores"] = sb.unpack()
+    if mb is not None:
+        out["maps"] = mb.unpack(spec[0])
+        out["maps_combined"] = out["maps"].pop("combined")
     return out

@@ -2,8 +2,8 @@
 caller's layouts: one table of field -> shape serves Session.outputs and meta_fit_node."""
 import numpy as np
 
-from ._lib import (CRIT_NAMES, N_CRIT, N_DIAG, N_LEVELS, N_SCORE, SCORE_NAMES, Criteria, Diagnostics, Outputs, Scores,
-                   Validation, dptr)
+from ._lib import (CRIT_NAMES, MAP_BASE_NAMES, N_CRIT, N_DIAG, N_LEVELS, N_MAP_BASE, N_SCORE, SCORE_NAMES, Criteria,
+                   Diagnostics, MapSpec, Maps, Outputs, Scores, Validation, dptr)
 
 # The array libmk fills for each mk_outputs field, row-major, in terms of: K subsets, P parameters,
 # C = q n_test kriging columns, L levels, n = n_samples, kept states, B amcmc batches, R = P + 1
@@ -152,4 +152,39 @@ class ScoreBuffers:
             out["combined"] = dict(zip(SCORE_NAMES, self.combined.tolist()))
         if self.combined_pointwise is not None:
             out["combined_pointwise"] = self.combined_pointwise.T.copy()
+        return out
+
+
+def map_spec(thresholds):
+    """Exceedance thresholds as libmk reads them: (the array, the mk_map_spec pointing at it).  libmk checks
+    them (finite, at most MK_MAP_MAXT)."""
+    u = np.ascontiguousarray(np.asarray(thresholds, dtype=np.float64).reshape(-1))
+    m = MapSpec()
+    m.thresholds, m.n_thresholds = (dptr(u) if u.size else None), int(u.size)
+    return u, m
+
+
+def map_names(J, base=MAP_BASE_NAMES):
+    return list(base) + [f"exc_{j + 1}" for j in range(int(J))]
+
+
+class MapBuffers:
+    """The arrays behind an mk_maps of K subsets with C = q n_test test columns and J thresholds: `.c`
+    points at them; unpack() gives {'names': w_mean, w_sd, p_mean, p_sd, exc_1..J, 'thresholds', 'subsets':
+    per subset a C x (4 + J) array} and, with combined, 'combined' (C x (4 + J))."""
+
+    def __init__(self, K, C, J, subsets=True, combined=False):
+        self.K, self.C, self.J = int(K), int(C), int(J)
+        n = N_MAP_BASE + self.J
+        self.subsets = np.zeros((self.K, n, self.C)) if subsets else None
+        self.combined = np.zeros((n, self.C)) if combined else None
+        self.c = Maps()
+        self.c.subsets, self.c.combined = dptr(self.subsets), dptr(self.combined)
+
+    def unpack(self, thresholds=()):
+        out = {"names": map_names(self.J), "thresholds": [float(u) for u in thresholds]}
+        if self.subsets is not None:
+            out["subsets"] = [self.subsets[i].T.copy() for i in range(self.K)]
+        if self.combined is not None:
+            out["combined"] = self.combined.T.copy()
         return out

@@ -10,7 +10,8 @@ import numpy as np
 
 from . import _lib
 from ._lib import Config, Problem, check, dptr, iptr
-from .outbuf import CriteriaBuffers, DiagnosticBuffers, OutputBuffers, ScoreBuffers, validation_arrays
+from .outbuf import (CriteriaBuffers, DiagnosticBuffers, MapBuffers, OutputBuffers, ScoreBuffers, map_names, map_spec,
+                     validation_arrays)
 
 COV_MODELS = {"exponential": _lib.MK_COV_EXPONENTIAL, "matern": _lib.MK_COV_MATERN}
 LINKS = {"logit": _lib.MK_LINK_LOGIT, "probit": _lib.MK_LINK_PROBIT}
@@ -21,6 +22,7 @@ LINKS = {"logit": _lib.MK_LINK_LOGIT, "probit": _lib.MK_LINK_PROBIT}
 KS_DIAG = 14      # the chain-diagnostic launches (always timed; 0 launches unless diagnostics were asked for)
 KS_CRIT = 15      # the model-assessment launches (always timed; 0 launches unless criteria were asked for)
 KS_SCORE = 16     # the held-out scoring launches (always timed; 0 launches unless validation data were attached)
+KS_MAPS = 17      # the posterior-map launches (always timed; 0 launches unless maps were asked for)
 
 
 def _f64(a):
@@ -186,6 +188,7 @@ class Session:
         self._h = h
         self._lib = lib
         self._window = None     # kept states of the next outputs(), once set_kept_window narrowed them
+        self._map_thresholds = None     # set_maps' thresholds while maps are attached
         # kriging fused into the kept iterations (mk_session_create's rule): a kept window then serves
         # criteria() alone, outputs() keeps every kept state
         self._fused = not (cfg.predict_tile > 0 and (self.n_test == 0 or cfg.predict_tile < self.n_test))
@@ -232,6 +235,7 @@ class Session:
         self.n_test = int(ct.shape[0])
         self.coords_test = _f64(ct.ravel(order="F"))
         self.x_test = None
+        self._map_thresholds = None     # the library detaches the maps with the sites
         check(self._lib.mk_session_set_test_sites(self._h, self.n_test, dptr(self.coords_test)))
         if xt is not None:
             self.set_test_covars(xt, _flat=True)
@@ -327,6 +331,30 @@ class Session:
         sb = ScoreBuffers(self.S, self.q * self.n_test, pointwise=pointwise)
         check(self._lib.mk_session_scores(self._h, ctypes.byref(sb.c)))
         return sb.unpack()
+
+    def set_maps(self, thresholds=()):
+        """Ask for the posterior maps at the current test sites (mk_session_set_maps): per test column the
+        mean and sd of w and of p(y = 1) and, per threshold u (probability scale, at most 8), the
+        posterior probability that p > u.  Needs test sites and x_test.  maps() then gives the planes; a
+        tiled session fills each tile's columns from the replay that makes its grids (outputs(),
+        tile_grids()).  thresholds=None detaches; so does set_test_sites."""
+        self._map_thresholds = None
+        if thresholds is None:
+            check(self._lib.mk_session_set_maps(self._h, None))
+            return
+        u, m = map_spec(thresholds)
+        check(self._lib.mk_session_set_maps(self._h, ctypes.byref(m)))
+        self._map_thresholds = u
+
+    def maps(self):
+        """The posterior maps per subset after the run (mk_session_maps; the definitions are in
+        include/mk.h): {'names': w_mean, w_sd, p_mean, p_sd, exc_1..J, 'thresholds', 'subsets': per subset
+        (q n_test) x (4 + J)}.  A tiled session must have replayed every tile over the current kept window
+        since set_maps (MkError naming the first missing tile otherwise)."""
+        u = self._map_thresholds if self._map_thresholds is not None else np.zeros(0)
+        mb = MapBuffers(self.S, self.q * self.n_test, u.size)
+        check(self._lib.mk_session_maps(self._h, ctypes.byref(mb.c)))
+        return mb.unpack(u)
 
     def set_lookahead(self, mode):
         """Launch schedule before the first run: True / 1 lookahead (the next iteration's phi
@@ -479,6 +507,23 @@ def score_grid(p, y, weights=1, pointwise=False, device=0):
     if pointwise:
         out["pointwise"] = pw.T.copy()
     return out
+
+
+def map_grid(grid, thresholds=(), device=0):
+    """Mean, sd and exceedance probabilities of a grid on the device (mk_map_grid; the kernel the sessions
+    use): grid is n_rows x C, its rows equally weighted states per column -- the combined 200-level grids
+    result2 or result3, say.  Returns {'names': mean, sd, exc_1..J, 'thresholds', 'planes': C x (2 + J)}: the
+    sd is Welford's over the rows in order (NaN for one row), exc_j the share of rows > thresholds[j]."""
+    lib = _lib.load()
+    g = np.asarray(grid, dtype=np.float64)
+    if g.ndim != 2:
+        raise ValueError("error: map_grid takes a 2-d array (states x columns)")
+    n, C = g.shape
+    cols = _f64(g.T)                                          # one contiguous column of states per row
+    u, _m = map_spec(thresholds)
+    out = np.zeros((2 + u.size, C))
+    check(lib.mk_map_grid(dptr(cols), int(n), int(C), dptr(u) if u.size else None, int(u.size), dptr(out), int(device)))
+    return {"names": map_names(u.size, ("mean", "sd")), "thresholds": u.tolist(), "planes": out.T.copy()}
 
 
 def correlation_batched(coords, phi, nu=None, cov_model="exponential", device=0):

@@ -199,6 +199,40 @@ def spValidate(sp_obj, pred_coords, pred_covars, y, weights=1, start=1, end=None
     return res
 
 
+def spMaps(sp_obj, pred_coords, pred_covars, thresholds=(), start=1, end=None):
+    """Posterior maps of an spMvGLM fit at pred_coords, on the device: per prediction column ((q n_test),
+    location-major like pred_covars' rows) the posterior mean and sd of w and of p(y = 1) and, per
+    threshold u (probability scale), the posterior probability that p > u, over iterations start..end
+    (1-based, inclusive), kriged from the recorded chain in one replay -- the draws never leave the
+    device.  Returns {"w.mean", "w.sd", "p.mean", "p.sd"} (each q n_test) plus "exceedance" ((q n_test) x
+    J) and "thresholds".  The definitions are in include/mk.h."""
+    ses = sp_obj.get("_session")
+    if ses is None:
+        raise ValueError("error: the spMvGLM fit was closed; spMaps needs its recorded chain states")
+    n_samples = sp_obj["_n_samples"]
+    end = n_samples if end is None else int(end)
+    start = int(start)
+    if not (1 <= start <= end <= n_samples):
+        raise ValueError("error: invalid start/end")
+    ct = np.asarray(pred_coords, float).reshape(-1, 2)
+    xt = np.asarray(pred_covars, float)
+    if xt.ndim != 2 or xt.shape[0] != ses.q * ct.shape[0]:
+        raise ValueError("error: pred.covars must have one row per prediction site and outcome (q * n rows)")
+    ses.set_test_sites(ct, x_test=pred_covars)
+    ses.set_kept_window(start, end)
+    ses.set_maps(thresholds)
+    try:
+        ses.outputs(quantiles=False, w_predict_sum=True)      # the one replay of the window
+        m = ses.maps()
+    finally:
+        ses.set_maps(None)
+    pl = m["subsets"][0]
+    res = {k.replace("_", "."): pl[:, i].copy() for i, k in enumerate(m["names"][:4])}
+    res["exceedance"] = pl[:, 4:].copy()
+    res["thresholds"] = m["thresholds"]
+    return res
+
+
 def spPredict(sp_obj, pred_coords, pred_covars=None, start=1, end=None, thin=1, diagnostics=False):
     """p.w.predictive.samples ((q n_test) x kept) for kept iterations start..end (1-based,
     inclusive; every thin-th), kriged from the chain states spMvGLM recorded (no refit).

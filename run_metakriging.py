@@ -72,7 +72,15 @@ def main():
                     help="held-out validation against y.test (log score, Brier score, error rate on the device): "
                          "one more JSON line, {\"validation\": the combined p grid's row, the median subset's row, "
                          "AUC}; several ranks: rank 0 scores the combined grid, per-subset rows are left out")
+    ap.add_argument("--maps", default=None, metavar="U1,U2,...",
+                    help="posterior maps of the combined posterior, e.g. 0.2,0.5 (at most 8 thresholds on the "
+                         "probability scale; '' for none): per test column the mean and sd of w and of p(y = 1) "
+                         "and P(p > u) per threshold, made on the device and saved as a (q n_test) x (4 + J) "
+                         ".npy (--maps-out); one more JSON line, {\"maps\": the file, the planes' names, per "
+                         "threshold the share of sites whose exceedance probability is >= 0.95}")
+    ap.add_argument("--maps-out", default="maps_combined.npy", help="where --maps saves the combined planes")
     a = ap.parse_args()
+    a.map_thresholds = None if a.maps is None else [float(u) for u in a.maps.split(",") if u.strip()]
     c = dict(CONFIGS[a.config])
     for k_arg, k_cfg in [("n", "n"), ("subsets", "K"), ("n_test", "n_test"), ("n_batch", "n_batch"),
                          ("batch_length", "batch_length"), ("predict_tile", "predict_tile")]:
@@ -88,6 +96,7 @@ def main():
     if a.criteria and world > 1:
         ap.error("--criteria runs in one process: plain, or over several GPUs with --devices")
     local = int(os.environ.get("LOCAL_RANK", "0"))
+    need_p = a.validate or a.map_thresholds is not None      # the combined grid of p(y = 1), result3
     dist = None
     if world > 1:
         import torch
@@ -120,7 +129,7 @@ def main():
     if subs:
         # one process, fused kriging: x.test goes in as MK.R:87 passes it, p.predict comes out
         ses = mk.Session(subs, cfg, coords_test=d["coords_test"], subset_base=lo, device=local,
-                         x_test=d["x_test"] if ((world == 1 and not big) or a.validate) else None,   # MK.R:108
+                         x_test=d["x_test"] if ((world == 1 and not big) or need_p) else None,   # MK.R:108
                          criteria=a.criteria)
         if a.validate and world == 1:             # scored per subset: now (fused) or by the tile replays
             ses.set_validation(d["y_test"])
@@ -174,14 +183,14 @@ def main():
                                  f"limits differ); pass --predict-tile {int(tl[0])} or less")
         if not big:
             result2 = dmod.combine_sharded(shard_grids(1, C), K, dist, method=a.combine, device=dev, gpu=local)
-            if a.validate:
+            if need_p:
                 result3 = dmod.combine_sharded(shard_grids(2, C), K, dist, method=a.combine, device=dev, gpu=local)
         else:
             # tiled kriging (cfg5): per test-site tile, the column-sharded exchange + combine of that
             # tile's grids (sequential mean, or the Weiszfeld median per column)
             result2 = dmod.combine_tiles(tile_grids, c["n_test"], tile, q, K, dist, method=a.combine, device=dev,
                                          gpu=local)
-            if a.validate:      # the p grids of every tile: a second replay (the exchange takes one kind at a time)
+            if need_p:          # the p grids of every tile: a second replay (the exchange takes one kind at a time)
                 def tile_grids_p(t0):
                     tc = min(tile, c["n_test"] - t0)
                     return ses.tile_grids(t0, prob=True)[1] if ses is not None else np.zeros((0, 200, q * tc))
@@ -197,17 +206,17 @@ def main():
         result = mk.combine_results([{"parameters": g} for g in out["parameters"]], device=local,
                                     method=a.combine)[0]
         result2 = np.zeros((200, C))
-        if a.validate:
+        if need_p:
             result3 = np.zeros((200, C))
         if a.diagnostics:    # the worst rows over the subsets, filled tile by tile from each tile's own replay
             diag["w_predict_diag_worst"] = np.zeros((3, C))
         for t0 in range(0, c["n_test"], tile):
-            if a.diagnostics or a.validate:     # one replay: the grids, the tile's diagnostics and its scores
-                res = ses.tile_grids(t0, prob=a.validate, diagnostics=a.diagnostics)
+            if a.diagnostics or need_p:         # one replay: the grids, the tile's diagnostics and its scores
+                res = ses.tile_grids(t0, prob=need_p, diagnostics=a.diagnostics)
                 g = res[0] if isinstance(res, tuple) else res
                 if a.diagnostics:
                     diag["w_predict_diag_worst"][:, t0 * q:t0 * q + g.shape[2]] = res[-1]["w_predict_diag_worst"]
-                if a.validate:
+                if need_p:
                     result3[:, t0 * q:t0 * q + g.shape[2]] = mk.combine_results(
                         [{"parameters": x} for x in res[1]], device=local, method=a.combine)[0]
             else:
@@ -247,6 +256,10 @@ def main():
             print(json.dumps({"criteria": dict(zip(crit["names"], crit["total"].tolist()))}), flush=True)
         if a.validate and result3 is not None:
             print(json.dumps({"validation": validation_line(mk, result3, d, scores, local)}), flush=True)
+        if a.map_thresholds is not None and result3 is not None:
+            w, p = (mk.map_grid(np.asarray(g), u, device=local) for g, u in ((result2, ()), (result3, a.map_thresholds)))
+            names = ["w_" + k for k in w["names"]] + ["p_" + k for k in p["names"][:2]] + p["names"][2:]
+            print(json.dumps({"maps": maps_line(np.hstack([w["planes"], p["planes"]]), names, a)}), flush=True)
     if dist is not None:
         dist.destroy_process_group()
 
@@ -274,6 +287,15 @@ def validation_line(mk, result3, d, scores, device):
     return line
 
 
+def maps_line(planes, names, a):
+    """Saves the combined planes ((q n_test) x (4 + J)) and summarises them: per threshold the share of
+    test columns whose exceedance probability is >= 0.95."""
+    np.save(a.maps_out, planes)
+    exc = planes[:, 4:]
+    return {"file": a.maps_out, "names": list(names), "thresholds": a.map_thresholds,
+            "share_exc_ge_0.95": [float(np.mean(exc[:, j] >= 0.95)) for j in range(exc.shape[1])]}
+
+
 def node_main(a, c):
     """The script in one process over a device list (mk_meta_fit): shards, combine (mean or median,
     per test-site tile at configs[4]) and post-processing without torch or a second process."""
@@ -293,7 +315,7 @@ def node_main(a, c):
         d, K, q, cov_model=c["cov"], n_batch=c["n_batch"], batch_length=c["batch_length"], seed=a.seed,
         devices=devices, method=a.combine, predict_tile=c.get("predict_tile", 0), partition_method=a.partition,
         progress=progress, predictive=True,     # MK.R:87's x.test: the grids of p(y = 1) and result3
-        diagnostics=a.diagnostics, criteria=a.criteria, validate=a.validate)
+        diagnostics=a.diagnostics, criteria=a.criteria, validate=a.validate, maps=a.map_thresholds)
     ph["data_s"] = data_s
     rec = dict(config=a.config, workload=c, devices=devices, combine=a.combine, phases=ph,
                subset_iters_per_s=K * cfg.n_samples / ph["chains_s"])
@@ -313,6 +335,8 @@ def node_main(a, c):
         v = summ["validation"]
         print(json.dumps({"validation": {"combined": v["combined"], "median_subset": v["median_subset"],
                                          "auc": v["report"]["auc"]}}), flush=True)
+    if a.map_thresholds is not None:
+        print(json.dumps({"maps": maps_line(summ["maps"]["combined"], summ["maps"]["names"], a)}), flush=True)
 
 
 if __name__ == "__main__":
