@@ -554,6 +554,16 @@ int mk_correlation_batched(const double* coords, int32_t S, int32_t n, const dou
 int mk_cholesky_batched(const double* A, int32_t S, int32_t n, double* L_out, double* logdet_out,
                         double* inv_out, int32_t device);
 
+/* The block -> job map of the inverse levels' launches (k_inv_level), evaluated on the host by the
+ * kernel's own code; no GPU work.  One launch: level sz (tiles per block: 1, 2, 4, ... < nt), phase 0
+ * or 1, `count` listed factors of nt 128-tiles on a grid sized for max_entries, sub = 1, 4 or 16
+ * sub-tiles per 128-tile.  map 1: the cut over the XCDs by work, longest K ranges first (MK_INV_MAP's
+ * default); 0: the equal-count cut.  Returns the launch's grid; when out is not NULL, block b < min(grid,
+ * cap) gets out[5 b ..] = entry, pair, tile row i, tile column j, sub-tile, or five times -1 when it
+ * has no job. */
+int mk_inv_map_jobs(int32_t map, int32_t count, int32_t max_entries, int32_t nt, int32_t sz, int32_t phase,
+                    int32_t sub, int32_t* out, int32_t cap);
+
 /* Hardware queues the process's HIP runtime was started with (GPU_MAX_HW_QUEUES when HIP first
  * initialised; HIP's default is 4).  The lookahead schedule adds a kriging stream and a CU-masked
  * main stream only when there are >= 8 (streams beyond the queue count share queues and serialise,

@@ -183,6 +183,7 @@ EXPORTS = {
     "mk_partition_r": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _ip, _ip]),
     "mk_r_sample": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _ip]),
     "mk_r_sample_replace": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _ip]),
+    "mk_inv_map_jobs": (ctypes.c_int, [ctypes.c_int32] * 7 + [_ip, ctypes.c_int32]),
     "mk_set_hw_queues": (ctypes.c_int, [ctypes.c_int32]),
     "mk_hip_initialized": (ctypes.c_int, []),
     "mk_shutdown": (None, []),

@@ -27,7 +27,7 @@ __global__ void k_chol_diag(MatSet ms, const int* n_s, int h0, int hc, int k, do
                             const int* slist, const int* scount, int cj0, int cj1, int syrk);
 __global__ void k_inv_copydiag(MatSet ms, const int* list, const int* count);
 template <int TM>
-__global__ void k_inv_level(MatSet ms, const int* list, const int* count, int sz, int phase, int deal);
+__global__ void k_inv_level(MatSet ms, const int* list, const int* count, int sz, int phase, int deal, int map);
 __global__ void k_lauum(MatSet ms, const int* n_s, const int* list, const int* count);
 __global__ void k_qblocks(MatSet ms, const int* n_s, const int* list, const int* count);
 __global__ void k_take_border(Model md, MatSet ms, const int* list, const int* count, const double* zc);

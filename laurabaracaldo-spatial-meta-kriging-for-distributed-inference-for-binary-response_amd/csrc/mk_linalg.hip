@@ -1072,23 +1072,17 @@ __global__ __launch_bounds__(256) void k_inv_copydiag(MatSet ms, const int* __re
 // bits; the sub-tile instances keep the quadrant body.
 template <int TM>
 __global__ __launch_bounds__(256, 2) void k_inv_level(MatSet ms, const int* __restrict__ list,
-                                                      const int* __restrict__ count, int sz, int phase, int deal) {
+                                                      const int* __restrict__ count, int sz, int phase, int deal,
+                                                      int map) {
   extern __shared__ __attribute__((aligned(16))) double lds[];   // gb_lds_bytes(TM, TM)
   constexpr int SUBR = MK_NB / TM, SUB = SUBR * SUBR;
-  const int npairs = (ms.nt + 2 * sz - 1) / (2 * sz);
-  const int per = npairs * sz * sz;
-  int e, t;
-  if (!xcd_map(*count, per * SUB, &e, &t)) return;
-  const int st = t % SUB;
-  t /= SUB;
+  int e, p, i, j, st;
+  // map: cut over the XCDs by work, longest K ranges first; else xcd_map's equal counts (mk_types.hpp)
+  if (!(map ? inv_map_job(*count, ms.nt, sz, phase, SUB, blockIdx.x, &e, &p, &i, &j, &st)
+            : inv_xcd_job(*count, ms.nt, sz, phase, SUB, blockIdx.x, &e, &p, &i, &j, &st)))
+    return;
   const int sr = st % SUBR, sc = st / SUBR;
-  const int p = t / (sz * sz);
-  t %= sz * sz;
-  const int T0 = 2 * p * sz, B0 = T0 + sz;
-  // consecutive work items share the operand whose K range is the same for all of them:
-  // phase 0 a column j (W_TT(j:B0, j)), phase 1 a row i (W_BB(i, B0:i+1))
-  const int i = B0 + (phase == 0 ? t % sz : t / sz), j = T0 + (phase == 0 ? t / sz : t % sz);
-  if (i >= ms.nt) return;
+  const int B0 = 2 * p * sz + sz;
   const int sh = list[e];
   const int cur = ms.cur[sh];
   const long ld = ms.ld;
@@ -1136,9 +1130,9 @@ __global__ __launch_bounds__(256, 2) void k_inv_level(MatSet ms, const int* __re
     store_tile(Wm + i * MK_NB + ro + (long)j * MK_NB * ld + co, ld, acc);
   }
 }
-template __global__ void k_inv_level<128>(MatSet, const int*, const int*, int, int, int);
-template __global__ void k_inv_level<64>(MatSet, const int*, const int*, int, int, int);
-template __global__ void k_inv_level<32>(MatSet, const int*, const int*, int, int, int);
+template __global__ void k_inv_level<128>(MatSet, const int*, const int*, int, int, int, int);
+template __global__ void k_inv_level<64>(MatSet, const int*, const int*, int, int, int, int);
+template __global__ void k_inv_level<32>(MatSet, const int*, const int*, int, int, int, int);
 
 // Tiles (i,j), i >= j, of R^-1 = sum over rows l < n_s of W(l,i)^T W(l,j) (drops the bordered
 // row and the padding).  diag_only: tiles (i,i) into QB; otherwise the full symmetric Q.

@@ -150,6 +150,34 @@ static int inv_deal() {
   return on != 0;
 }
 
+// MK_INV_MAP (default 1, read once per process): the inverse levels' launches cut their tile jobs over
+// the XCDs by work and start the longest K ranges first (inv_map_job, mk_types.hpp); 0: xcd_map's cut
+// by item count in the matrices' item order, on its own grid.  An argument of the kernel, so one build
+// serves both arms of an A/B; only which workgroup computes which tile differs: same bits.
+static int inv_map() {
+  static const int on = env_int("MK_INV_MAP", 1);
+  return on != 0;
+}
+// Blocks of a level's launch for up to max_entries listed factors on sub sub-tiles per 128-tile.
+static int inv_grid(int map, int max_entries, int nt, int sz, int sub) {
+  if (map) return inv_map_grid(max_entries, nt, sz, sub);
+  return xcd_grid_h(max_entries, (nt + 2 * sz - 1) / (2 * sz) * sz * sz * sub);
+}
+// Test entry of the map (include/mk.h): the launch grid, and what each of its blocks computes, by the
+// kernel's own code on the host.
+extern "C" int mk_inv_map_jobs(int32_t map, int32_t count, int32_t max_entries, int32_t nt, int32_t sz, int32_t phase,
+                               int32_t sub, int32_t* out, int32_t cap) {
+  const int grid = inv_grid(map, max_entries, nt, sz, sub);
+  for (int b = 0; out && b < grid && b < cap; ++b) {
+    int e, p, i, j, st;
+    const bool job = map ? inv_map_job(count, nt, sz, phase, sub, b, &e, &p, &i, &j, &st)
+                         : inv_xcd_job(count, nt, sz, phase, sub, b, &e, &p, &i, &j, &st);
+    int32_t* o = out + 5 * (long)b;
+    o[0] = job ? e : -1, o[1] = job ? p : -1, o[2] = job ? i : -1, o[3] = job ? j : -1, o[4] = job ? st : -1;
+  }
+  return grid;
+}
+
 static void chol_update(mk_session* s, Group& g, hipStream_t st, int h0, int hc, int k, int ia, int ib, int j0, int j1,
                         const int* slist, const int* scount, double flops) {
   const int E = g.S * hc, nti = ib - ia;
@@ -372,6 +400,16 @@ void mk::launch_trinv(mk_session* s, Group& g, int max_entries, const int* list,
     // list (about 40% at the amcmc target rate) and the level's K ranges are uneven: price the
     // launch at an eighth of its 128-tile grid (measured: 32 subsets 1.33 -> 1.16 ms per iteration)
     const int tm = tile_size((long)max_entries * npairs * sz * sz / 8);
+    // the map's integers stay below 2^31 at every shape a session can hold (8 (entries + 1) work is
+    // 5e8 at nt = 64 with 250 entries); a launch past that keeps xcd_map, a correct placement, and
+    // says so once
+    const bool fits = inv_map_fits(max_entries, nt, sz);
+    if (inv_map() && !fits) {
+      static bool said = false;
+      if (!said) fprintf(stderr, "libmk: inverse level of %d entries, nt = %d: job map too large, equal-count cut used\n", max_entries, nt);
+      said = true;
+    }
+    const int map = inv_map() && fits;
     for (int phase = 0; phase < 2; ++phase) {
       // per listed factor: the mean over the group's subsets (exact for equal subset sizes)
       double per = 0.0;
@@ -379,16 +417,18 @@ void mk::launch_trinv(mk_session* s, Group& g, int max_entries, const int* list,
         for (int i = g.s0; i < g.s0 + g.S; ++i) per += inv_level_flops(s->n_part[i], nt, sz, phase);
         per /= std::max(1, g.S);
       }
+      const int sub = (MK_NB / tm) * (MK_NB / tm);
+      const int grid = inv_grid(map, max_entries, nt, sz, sub);
       auto launch = [&] {
         if (tm == 32)
-          MK_LAUNCH(k_inv_level<32>, dim3(xcd_grid_h(max_entries, npairs * sz * sz * 16)), dim3(256), LDS_32,
-                             g.stream, g.ms, list, count, sz, phase, inv_deal());
+          MK_LAUNCH(k_inv_level<32>, dim3(grid), dim3(256), LDS_32, g.stream, g.ms, list, count, sz, phase, inv_deal(),
+                    map);
         else if (tm == 64)
-          MK_LAUNCH(k_inv_level<64>, dim3(xcd_grid_h(max_entries, npairs * sz * sz * 4)), dim3(256), LDS_64,
-                             g.stream, g.ms, list, count, sz, phase, inv_deal());
+          MK_LAUNCH(k_inv_level<64>, dim3(grid), dim3(256), LDS_64, g.stream, g.ms, list, count, sz, phase, inv_deal(),
+                    map);
         else
-          MK_LAUNCH(k_inv_level<128>, dim3(xcd_grid_h(max_entries, npairs * sz * sz)), dim3(256), LDS_128,
-                             g.stream, g.ms, list, count, sz, phase, inv_deal());
+          MK_LAUNCH(k_inv_level<128>, dim3(grid), dim3(256), LDS_128, g.stream, g.ms, list, count, sz, phase,
+                    inv_deal(), map);
       };
       if (cnt >= 0)
         timed(s, g.stream, KS_INV, per, launch, cnt);

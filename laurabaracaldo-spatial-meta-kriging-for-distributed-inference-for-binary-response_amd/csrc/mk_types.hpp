@@ -175,9 +175,9 @@ __device__ inline Key subset_key(const Model& md, int s) { return make_key(md.se
 // are active (a short list of changed subsets no longer leaves XCDs idle).  S is the number of
 // ACTIVE entries; the grid (xcd_grid of the maximum) covers any S up to that maximum.  Speed
 // only; any placement is correct.
-__device__ inline bool xcd_map(int S, int T, int* s, int* t) {
+__host__ __device__ inline bool xcd_map_at(int b, int S, int T, int* s, int* t) {
   const int W = S * T, C = (W + 7) >> 3;
-  const int x = blockIdx.x & 7, j = blockIdx.x >> 3;
+  const int x = b & 7, j = b >> 3;
   if (j >= C) return false;
   const int w = x * C + j;
   if (w >= W) return false;
@@ -185,6 +185,7 @@ __device__ inline bool xcd_map(int S, int T, int* s, int* t) {
   *t = w % T;
   return true;
 }
+__device__ inline bool xcd_map(int S, int T, int* s, int* t) { return xcd_map_at(blockIdx.x, S, T, s, t); }
 // The same map with every entry's last item (t = T - 1, T >= 2) dealt after all the others: XCD x
 // takes its chunk of the S (T - 1) leading items first, then its chunk of the S last items.  Fits
 // the same grid: ceil(S (T-1) / 8) + ceil(S / 8) <= ceil(S / 8) T.
@@ -205,6 +206,142 @@ __device__ inline bool xcd_map_tail(int S, int T, int* s, int* t) {
   return true;
 }
 __host__ inline int xcd_grid(int S, int T) { return 8 * ((S + 7) / 8) * T; }
+
+// ---------------------------------------------------------------- job map of the inverse levels
+// A k_inv_level launch (level sz, one phase) is the one GEMM launch whose jobs differ in length: tile
+// (i, j) of the pair T = [T0, T0+sz), B = [B0, B0+sz), B0 = T0 + sz, runs a K range of B0 - j tiles in
+// phase 0 and of i - B0 + 1 tiles in phase 1, 1 to sz of them.  xcd_map's cut by item count then gives the
+// XCDs unequal work, and its item order ends every XCD's share on the longest jobs of its last matrix.
+// inv_map_job cuts by work and starts the longest jobs first.
+//
+// Items.  Tiles with i >= nt do not exist; only the last pair of a matrix can lose rows to that, so a
+// matrix is F = nt / (2 sz) whole pairs and one of rl < sz rows (rl = 0: none).  Class k holds the
+// tiles whose K range is k tiles: in phase 0 column j = B0 - k of every pair (R = F sz + rl tiles, pair
+// by pair, rows ascending), in phase 1 row i = B0 + k - 1 of the pairs that have it (sz tiles each, pair
+// by pair, columns ascending) -- so the tiles that share a triangular operand are consecutive.  An
+// item is one workgroup's job: a tile, or one of its SUB sub-tiles (adjacent items, each the tile's K
+// range on 1 / SUB of its elements; work is counted in these units, k per item of class k).  The
+// item sequence of a launch is entry-major and, within a matrix, class-major from k = sz down; all
+// matrices of a session have the same nt, hence the same sequence, of SUB sz R items.
+//
+// Cut.  XCD x (blocks b with b % 8 = x) takes the contiguous run of items whose work midpoint lies in
+// the x-th eighth of the launch's work: with c the work before an item of class k and Wt the total,
+// x Wt <= 8 c + 4 k < (x + 1) Wt.  Both ends of a run are within sz / 2 of the ideal cut, so an XCD's
+// work is within one longest job of the mean; a matrix lies on one XCD, or on two at a cut (the shared
+// operands' L2 reuse, above).  The midpoints of one matrix lie inside its own stretch of the work
+// line, so a run of width <= ceil(S / 8) matrices touches at most ceil(S / 8) + 1 of them:
+// inv_map_grid, which covers any listed count up to max_entries.
+//
+// Order.  Within its run an XCD takes class sz of all its matrices first, then sz - 1, ...: within a
+// class by entry, then in the matrix's order, so the sub-tiles of a tile stay adjacent (a cut may fall
+// between two of them).  The blocks past an XCD's run are the last of its blocks, as with xcd_map.
+//
+// Cost per block: two cuts and one class search, O(sz) integer steps and five divisions; every
+// quantity is below 8 (S + 1) Wm, which inv_map_fits checks against 2^31 on the host.
+struct InvShape {
+  int sz, phase, sub, F, rl;
+  // items of class k, items and work of a matrix
+  __host__ __device__ int n(int k) const { return sub * (phase == 0 ? F * sz + rl : sz * (F + (rl >= k ? 1 : 0))); }
+  __host__ __device__ int items() const { return sub * sz * (F * sz + rl); }
+  __host__ __device__ int work() const {
+    const int full = sz * (sz + 1) / 2;
+    return sub * (phase == 0 ? (F * sz + rl) * full : sz * (F * full + rl * (rl + 1) / 2));
+  }
+};
+__host__ __device__ inline InvShape inv_shape(int nt, int sz, int phase, int sub) {
+  InvShape h;
+  h.sz = sz;
+  h.phase = phase;
+  h.sub = sub;
+  h.F = nt / (2 * sz);
+  const int rem = nt - 2 * sz * h.F;
+  h.rl = rem > sz ? rem - sz : 0;
+  return h;
+}
+struct InvPos { int e, k, m; };   // the m-th item of class k of entry e
+// The first item whose work midpoint is at or past x eighths of the work of S matrices.
+__host__ __device__ inline InvPos inv_map_cut(const InvShape& h, int S, int x) {
+  // 8 c + 4 k >= x S Wm: entry x S / 8, and within it the threshold tl on the matrix's own work line
+  InvPos q;
+  q.e = (x * S) >> 3;
+  const int tl = ((x * S) & 7) * h.work();
+  int A = 0;   // work before class k
+  for (int k = h.sz; k >= 1; --k) {
+    const int nk = h.n(k), num = tl - 8 * A - 4 * k;
+    // item m of the class has midpoint (8 (A + m k) + 4 k) / 8: the first with 8 k m >= num
+    if (nk > 0 && num <= 8 * k * (nk - 1)) {
+      q.k = k;
+      q.m = num <= 0 ? 0 : (num + 8 * k - 1) / (8 * k);
+      return q;
+    }
+    A += nk * k;
+  }
+  q.e += 1;   // past the matrix's last midpoint: the next matrix's first item
+  q.k = h.sz;
+  q.m = 0;
+  return q;
+}
+// Items of class k that a matrix has before position q (q.k, q.m).
+__host__ __device__ inline int inv_before(const InvShape& h, const InvPos& q, int k) {
+  return k > q.k ? h.n(k) : (k == q.k ? q.m : 0);
+}
+// Block b of a level's launch over S listed entries -> entry e, pair p, tile (i, j), sub-tile st < SUB.
+__host__ __device__ inline bool inv_map_job(int S, int nt, int sz, int phase, int SUB, int b, int* e, int* p, int* i,
+                                            int* j, int* st) {
+  if (S <= 0) return false;
+  const InvShape h = inv_shape(nt, sz, phase, SUB);
+  const int x = b & 7;
+  int q = b >> 3;   // the item's rank in the XCD's run
+  const InvPos a = inv_map_cut(h, S, x), z = inv_map_cut(h, S, x + 1);
+  for (int k = sz; k >= 1; --k) {
+    const int nk = h.n(k), ba = inv_before(h, a, k);
+    const int cnt = (z.e - a.e) * nk + inv_before(h, z, k) - ba;
+    if (q >= cnt) {
+      q -= cnt;
+      continue;
+    }
+    const int g = a.e * nk + ba + q;   // ordinal among the launch's class-k items
+    *e = g / nk;
+    *st = g % SUB;
+    const int m = g % nk / SUB;        // the tile among the matrix's class-k tiles
+    if (phase == 0) {
+      const bool last = m >= h.F * sz;   // the short pair's rl rows
+      *p = last ? h.F : m / sz;
+      *i = 2 * *p * sz + sz + (last ? m - h.F * sz : m % sz);
+      *j = 2 * *p * sz + sz - k;
+    } else {
+      *p = m / sz;
+      *i = 2 * *p * sz + sz + k - 1;
+      *j = 2 * *p * sz + m % sz;
+    }
+    return true;
+  }
+  return false;
+}
+// The same answer from xcd_map (MK_INV_MAP=0): the matrices' npairs sz^2 tile slots per entry in equal
+// counts, clipped tiles (i >= nt) included and dropped here.
+__host__ __device__ inline bool inv_xcd_job(int S, int nt, int sz, int phase, int SUB, int b, int* e, int* p, int* i,
+                                            int* j, int* st) {
+  const int npairs = (nt + 2 * sz - 1) / (2 * sz);
+  int t;
+  if (!xcd_map_at(b, S, npairs * sz * sz * SUB, e, &t)) return false;
+  *st = t % SUB;
+  t /= SUB;
+  *p = t / (sz * sz);
+  t %= sz * sz;
+  // consecutive work items share the operand whose K range is the same for all of them:
+  // phase 0 a column j (W_TT(j:B0, j)), phase 1 a row i (W_BB(i, B0:i+1))
+  *i = 2 * *p * sz + sz + (phase == 0 ? t % sz : t / sz);
+  *j = 2 * *p * sz + (phase == 0 ? t / sz : t % sz);
+  return *i < nt;
+}
+__host__ inline bool inv_map_fits(int max_entries, int nt, int sz) {
+  const long w = std::max(inv_shape(nt, sz, 0, 16).work(), inv_shape(nt, sz, 1, 16).work());
+  return 8L * ((long)max_entries + 1) * w < (1L << 31);
+}
+__host__ inline int inv_map_grid(int max_entries, int nt, int sz, int SUB) {
+  return 8 * ((max_entries + 7) / 8 + 1) * inv_shape(nt, sz, 0, SUB).items();
+}
 
 
 }  // namespace mk
