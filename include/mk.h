@@ -85,7 +85,12 @@ typedef struct mk_config {
                                    Else the kept chain states are recorded and the kriging
                                    runs after the fit over tiles of this many test sites, so
                                    (q*n_test) x kept draws per subset never coexist (cfg5:
-                                   1M sites); results are identical either way            */
+                                   1M sites).  The exact replay gives the fused draws bit for
+                                   bit.  Exponential sessions (any q) whose kept window is long
+                                   enough for it to save exact evaluations interpolate the
+                                   kriging variance in phi per (subset, outcome) pair
+                                   (MK_KRIG_CHEB): the draws then agree with the
+                                   fused ones to 1e-8 absolute, not bit for bit               */
   int32_t link;                 /* MK_LINK_LOGIT (the reference) or MK_LINK_PROBIT              */
 } mk_config;
 
@@ -185,10 +190,12 @@ int mk_session_tile_grids_wp(mk_session* s, int32_t t0, double* out_w, double* o
  * inverses); 7 kind 0's 64/32-sub-tile instances; 8 kinds 0 + 7 with overlapping launches counted
  * once; 9 kriging GEMM k_pred_var; 10 candidate covariance assembly; 11 latent sweeps the
  * multi-workgroup kernel refused admission and its fallback ran -- launches = (subset, iteration)
- * count, no timing; 12 tiles of a tiled session kriged by phi interpolation -- launches = tiles, flops
- * = exact kriging-variance evaluations, total_ms = the largest per-tile check difference (not a time);
- * 13 tiles whose check failed and were replayed exactly -- launches, total_ms = the largest failing
- * difference; 14 the chain-diagnostic launches k_chain_diag / k_chain_diag_prob -- launches and ms,
+ * count, no timing; 12 tiles of a tiled session kriged by phi interpolation (exponential, any q) --
+ * launches = tiles, flops = exact kriging-variance evaluations, one per (subset, outcome) pair and node
+ * or check point, total_ms = the largest per-tile check difference over all pairs and sites (not a
+ * time; a fused q = 1 session drawing from phi tables counts its kept iterations here instead); 13
+ * tiles whose check failed at any pair and were replayed exactly -- launches, total_ms = the largest
+ * failing difference; 14 the chain-diagnostic launches k_chain_diag / k_chain_diag_prob -- launches and ms,
  * timed whether or not profiling is on; 0 launches unless diagnostics were asked for; 15 the
  * model-assessment launches k_crit_accum / k_crit_replay / k_crit_finish / k_crit_total -- launches and
  * ms, always timed, 0 launches unless criteria were asked for; 16 the held-out scoring launches

@@ -123,6 +123,7 @@ __global__ void k_cheb_check(Model md, ChebK c, unsigned long long* err);
 __global__ void k_kt_snap(Model md, double* zs, double* phis, double* As);
 __global__ void k_pred_tab_draw(Model md, ChebK c, const double* g, const double* coords, const double* phis,
                                 const double* As, int iter, int kidx);
+template <int Q>
 __global__ void k_pred_cheb_draw(Model md, ChebK c, const double* Gt, const double* phit, const double* coords,
                                  const double* kA, int k_lo, int nkp);
 // mk_criteria.hip

@@ -250,10 +250,11 @@ static int tile_outputs(mk_session* s, int t0, double* dq, double* dqp, mk_outpu
 }
 
 // ------------------------------------------------------------------ kriging variance by phi interpolation
-// (exponential, q = 1; DESIGN.md 4.7, mk_mcmc.hip section 11).  s(t; phi) = rho_t' R(phi)^-1 rho_t is
-// analytic in phi: it is computed exactly (the replay's own kernels: candidate, Cholesky, inverse,
-// X = W P^T) at nc Chebyshev nodes (first kind) of a phi range per subset and interpolated (barycentric)
-// wherever a draw needs it.  nc = 6 + ceil((phi_hi - phi_lo) * d_max), at least 10, at most 32 (d_max:
+// (exponential; the tiled replay for any q, the fused tables for q = 1; DESIGN.md 4.7, mk_mcmc.hip
+// section 11).  s(t; phi) = rho_t' R(phi)^-1 rho_t is analytic in phi: it is computed exactly (the
+// replay's own kernels: candidate, Cholesky, inverse, X = W P^T) at nc Chebyshev nodes (first kind) of a
+// phi range per (subset, outcome) pair and interpolated (barycentric) wherever a draw needs it.
+// nc = 6 + ceil((phi_hi - phi_lo) * d_max), at least 10, at most 32 (d_max:
 // the subset's largest site-to-site or site-to-test-site distance, so the rule counts the range in units
 // of the correlation decay; measured in float64 on 2,000-site subsets with clustered sites and test
 // sites 1e-6 from a site, d_max 1.41: |error| 2e-14 over phi in [3.3, 11.8] with the rule's 18 nodes,
@@ -266,18 +267,19 @@ static int tile_outputs(mk_session* s, int t0, double* dq, double* dqp, mk_outpu
 // applicable, scratch memory short, a check failed), and an MK_E_* code (< 0) on an error.
 constexpr int MK_CHEB_EXACT = 1;
 
-// Nodes of [lo, hi] for each subset: nc[i], the slots' phi (nodes, then nchk check points) and the
-// barycentric weights.  Returns the slot count E (the largest nc + nchk).
+// Nodes of [lo, hi] for each (subset, outcome) pair i = s q + h: nc[i], the slots' phi (nodes, then nchk
+// check points) and the barycentric weights; d_max is the subset's.  Returns the slot count E (the
+// largest nc + nchk).
 static int cheb_plan(mk_session* s, const std::vector<double>& lo, const std::vector<double>& hi, int force_n, int nchk,
                      std::vector<int>& nc, std::vector<std::vector<double>>& sphi, std::vector<double>& wts) {
-  const int S = s->S;
+  const int S = s->S * s->q;
   nc.assign(S, 0);
   sphi.assign(S, {});
   wts.assign((size_t)S * MK_CHEB_MAX, 0.0);
   int E = 0;
   for (int i = 0; i < S; ++i) {
-    const double* bb = s->bbox.data() + 4 * i;
-    const double dmax = std::fmax(s->span_pt_h[i], std::hypot(bb[1] - bb[0], bb[3] - bb[2]));
+    const double* bb = s->bbox.data() + 4 * (i / s->q);
+    const double dmax = std::fmax(s->span_pt_h[i / s->q], std::hypot(bb[1] - bb[0], bb[3] - bb[2]));
     const int n = force_n > 1 ? std::min(force_n, MK_CHEB_MAX)
                               : std::max(10, std::min(MK_CHEB_MAX, 6 + (int)std::ceil((hi[i] - lo[i]) * dmax)));
     nc[i] = n;
@@ -294,54 +296,76 @@ static int cheb_plan(mk_session* s, const std::vector<double>& lo, const std::ve
   return E;
 }
 
-// Exact s of every planned slot into Sn ([slot][S][n_test_pad] of mt's sites) and the slots' device phi
-// into nphi; then the interpolant against the check points (largest difference into *emax).  The factor
-// slots, cur and W serve as scratch: callers are the tiled replay (the chain is finished) and session
-// set-up (before the initial factorisation).  The host stays at most four slots ahead of the device.
+// Exact s of every planned slot into Sn ([slot][S q][n_test_pad] of mt's sites) and the slots' device phi
+// into nphi; then the interpolant against the check points (largest difference over pairs and sites
+// into *emax).  Slot e is one pass of the replay's own kernels over the pairs that have a slot e, all
+// outcomes of a subset together: its theta record carries each outcome's own slot-e phi_h, and the
+// lists are the replay's (per outcome the subsets, then the pairs sh = s q + h).  A pair with fewer
+// slots than E is simply not listed past its last one -- nothing is factored or refreshed for it, and
+// its rows of the later slots of Sn stay zero and unread (its unused phi_h in those records repeats
+// its first node, so the record stays a valid theta).  The factor slots, cur and W serve as scratch:
+// callers are the tiled replay (the chain is finished) and session set-up (before the initial
+// factorisation).  The host stays at most four slots ahead of the device.
 static int cheb_eval(mk_session* s, Model mt, const std::vector<int>& nc, const std::vector<std::vector<double>>& sphi,
                      const std::vector<double>& wts, int E, int nchk, DevBufs& scratch, ChebK* ck, double* emax) {
   Model& md = s->md;
-  const int S = s->S, nth = md.n_theta, T_pad = md.n_test_pad;
-  const double pa = md.phi_a[0], pb = md.phi_b[0];
+  const int S = s->S, q = s->q, SQ = S * q, nth = md.n_theta, T_pad = md.n_test_pad;
   hipStream_t st = s->stream;
   Group g = s->all;
   // slot e's theta (phi in the candidate's logit form; the device's phi of it is what counts) and its
-  // subset list (the subsets with that many slots)
+  // lists: [q][S] subsets per outcome, [q] their counts, [S q] pairs (outcome-major, as k_kept_dirty
+  // lists them), [1] their count
+  const size_t LS = (size_t)2 * SQ + q + 1;
   std::vector<double> thn((size_t)E * S * nth, 0.0);
-  std::vector<int> lists((size_t)E * (S + 1), 0);
+  std::vector<int> lists((size_t)E * LS, 0);
   for (int e = 0; e < E; ++e) {
-    int cnt = 0;
-    for (int i = 0; i < S; ++i) {
-      const double ph = e < (int)sphi[i].size() ? sphi[i][e] : sphi[i][0];
-      thn[((size_t)e * S + i) * nth + md.ntri] = std::log((ph - pa) / (pb - ph));
-      if (e < (int)sphi[i].size()) lists[(size_t)e * (S + 1) + cnt++] = i;
+    int* L = lists.data() + (size_t)e * LS;
+    int pc = 0;
+    for (int h = 0; h < q; ++h) {
+      const double pa = md.phi_a[h], pb = md.phi_b[h];
+      int cnt = 0;
+      for (int i = 0; i < S; ++i) {
+        const std::vector<double>& sp = sphi[(size_t)i * q + h];
+        const bool has = e < (int)sp.size();
+        const double ph = has ? sp[e] : sp[0];
+        thn[((size_t)e * S + i) * nth + md.ntri + h] = std::log((ph - pa) / (pb - ph));
+        if (has) {
+          L[h * S + cnt++] = i;
+          L[SQ + q + pc++] = i * q + h;
+        }
+      }
+      L[SQ + h] = cnt;
     }
-    lists[(size_t)e * (S + 1) + S] = cnt;
+    L[2 * SQ + q] = pc;
   }
   double* d_thn = scratch.get<double>(thn.size());
-  double* d_nphi = scratch.get<double>((size_t)E * S);
+  double* d_nphi = scratch.get<double>((size_t)E * SQ);
   double* d_wts = scratch.get<double>(wts.size());
-  int* d_nc = scratch.get<int>((size_t)S);
+  int* d_nc = scratch.get<int>((size_t)SQ);
   int* d_lists = scratch.get<int>(lists.size());
-  double* d_Sn = scratch.get<double>((size_t)E * S * T_pad);
+  double* d_Sn = scratch.get<double>((size_t)E * SQ * T_pad);
   unsigned long long* d_err = scratch.get<unsigned long long>(1);
   if (!d_thn || !d_nphi || !d_wts || !d_nc || !d_lists || !d_Sn || !d_err) return MK_CHEB_EXACT;
   HIPCHK(hipMemcpyAsync(d_thn, thn.data(), thn.size() * 8, hipMemcpyHostToDevice, st));
   HIPCHK(hipMemcpyAsync(d_wts, wts.data(), wts.size() * 8, hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemcpyAsync(d_nc, nc.data(), (size_t)S * sizeof(int), hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(d_nc, nc.data(), (size_t)SQ * sizeof(int), hipMemcpyHostToDevice, st));
   HIPCHK(hipMemcpyAsync(d_lists, lists.data(), lists.size() * sizeof(int), hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemsetAsync(d_Sn, 0, (size_t)E * S * T_pad * 8, st));
+  HIPCHK(hipMemsetAsync(d_Sn, 0, (size_t)E * SQ * T_pad * 8, st));
   HIPCHK(hipMemsetAsync(d_err, 0, 8, st));
-  MK_LAUNCH(k_kept_phi, dim3((unsigned)(((long)E * S + 255) / 256)), dim3(256), 0, st, md, d_thn, E, d_nphi);
+  MK_LAUNCH(k_kept_phi, dim3((unsigned)(((long)E * SQ + 255) / 256)), dim3(256), 0, st, md, d_thn, E, d_nphi);
   for (int e = 0; e < E; ++e) {
-    int* L = d_lists + (size_t)e * (S + 1);
-    int* C = L + S;
+    int* SL = d_lists + (size_t)e * LS;   // subsets per outcome
+    int* SC = SL + SQ;
+    int* L = SC + q;                      // pairs
+    int* C = L + SQ;
     mt.theta = d_thn + (size_t)e * S * nth;
-    mt.s_pred = d_Sn + (size_t)e * S * T_pad;
-    launch_candidates(mt, g.ms, st, S, 0, 1, 2, 0, L, C);
-    launch_cholesky(s, g, 0, 1, L, C);
-    MK_LAUNCH(k_flip_pairs, dim3((S + 255) / 256), dim3(256), 0, st, g.ms, L, C);
-    launch_trinv(s, g, S, L, C);
+    mt.s_pred = d_Sn + (size_t)e * SQ * T_pad;
+    for (int h = 0; h < q; ++h) {
+      launch_candidates(mt, g.ms, st, S, h, 1, 2, 0, SL + h * S, SC + h);
+      launch_cholesky(s, g, h, 1, SL + h * S, SC + h);
+    }
+    MK_LAUNCH(k_flip_pairs, dim3((SQ + 255) / 256), dim3(256), 0, st, g.ms, L, C);
+    launch_trinv(s, g, SQ, L, C);
     Group gp = g;
     gp.md = mt;
     gp.d_plist = L;
@@ -356,7 +380,7 @@ static int cheb_eval(mk_session* s, Model mt, const std::vector<int>& nc, const 
   ck->nc = d_nc;
   ck->nchk = nchk;
   ck->T_pad = T_pad;
-  MK_LAUNCH(k_cheb_check, dim3(S * ((mt.n_test + 255) / 256)), dim3(256), 0, st, mt, *ck, d_err);
+  MK_LAUNCH(k_cheb_check, dim3(SQ * ((mt.n_test + 255) / 256)), dim3(256), 0, st, mt, *ck, d_err);
   unsigned long long eb = 0;
   HIPCHK(hipMemcpyAsync(&eb, d_err, 8, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
@@ -445,18 +469,20 @@ int mk::krig_tables(mk_session* s) {
   return 0;
 }
 
-// Tile [t0, t0 + Tc) of the tiled replay by phi interpolation: nodes over each subset's kept phi range,
-// checked at its ends and middle (a difference above MK_KRIG_CHEB_TOL, default 1e-10, sends the tile
-// to the exact replay: KS_KRIG_FALLBACK); the mean m_k(t) = rho_t(phi_k)' g_k with g_k = W_k' z_k made
-// once per kept window (the exact replay's factorisations where phi changed, one W' z per state).  At
-// configs[4]: ~490 X refreshes per subset and tile become 13-21 nodes + 3 checks.  Auto mode
-// (cheb_mode): where the nodes and checks cost fewer exact evaluations than the exact replay's refreshes.
+// Tile [t0, t0 + Tc) of the tiled replay by phi interpolation, per (subset, outcome) pair sh = s q + h
+// (under the LMC s_h, m_h and the normal are outcome h's own; A_k mixes them afterwards): nodes over each
+// pair's kept phi_h range, checked at its ends and middle (a difference above MK_KRIG_CHEB_TOL, default
+// 1e-10, at any pair and site sends the whole tile to the exact replay: KS_KRIG_FALLBACK); the mean
+// m_k,h(t) = rho_t(phi_k,h)' g_k,h with g_k,h = W_k,h' z_k,h made once per kept window (the exact replay's
+// factorisations where phi_h changed, one W' z per state and pair).  At configs[4] (q = 1): ~490 X
+// refreshes per subset and tile become 13-21 nodes + 3 checks.  Auto mode (cheb_mode): where the nodes
+// and checks of all pairs cost fewer exact evaluations than the exact replay's refreshes of all pairs.
 // Returns 0, MK_CHEB_EXACT (the exact replay must run) or an error (< 0).
 static int predict_tile_cheb(mk_session* s, int t0, double* dq, mk_outputs* o, double* dqp) {
   Model& md = s->md;
   const int force_n = cheb_mode();
-  if (force_n == 0 || s->q != 1 || md.cov_model != MK_COV_EXPONENTIAL) return MK_CHEB_EXACT;
-  const int S = s->S, nth = md.n_theta, n_pad = md.n_pad;
+  if (force_n == 0 || md.cov_model != MK_COV_EXPONENTIAL) return MK_CHEB_EXACT;
+  const int S = s->S, q = s->q, SQ = S * q, nth = md.n_theta, n_pad = md.n_pad;
   const int k_lo = s->win_lo, n_kept = s->win_n < 0 ? md.n_kept : s->win_n;
   if (n_kept < 1 || (int)s->span_pt_h.size() != S) return MK_CHEB_EXACT;
   const int T_pad = md.n_test_pad, Tc = std::min(s->pred_tile, s->n_test_all - t0);
@@ -464,33 +490,34 @@ static int predict_tile_cheb(mk_session* s, int t0, double* dq, mk_outputs* o, d
   Group g = s->all;
   s->la.next = -1;   // the replay factors into the free slots
   s->cov.pre = -1;
-  // 1. phi_k of the window's kept states (once per window)
+  // 1. phi_k,h of the window's kept states, [state][pair] (once per window)
   if (s->cg.iter != s->iter || s->cg.lo != k_lo || s->cg.n != n_kept) {
     s->release(s->cg.G);
     s->release(s->cg.phi);
     s->release(s->cg.phit);
     s->cg.G = s->cg.phi = s->cg.phit = nullptr;
     s->cg.iter = -1;
-    if (s->alloc(&s->cg.phi, (size_t)n_kept * S)) return MK_CHEB_EXACT;
-    MK_LAUNCH(k_kept_phi, dim3((unsigned)(((long)n_kept * S + 255) / 256)), dim3(256), 0, st, md,
+    if (s->alloc(&s->cg.phi, (size_t)n_kept * SQ)) return MK_CHEB_EXACT;
+    MK_LAUNCH(k_kept_phi, dim3((unsigned)(((long)n_kept * SQ + 255) / 256)), dim3(256), 0, st, md,
               md.kth + (long)k_lo * S * nth, n_kept, s->cg.phi);
-    s->cg.phi_h.assign((size_t)n_kept * S, 0.0);
-    HIPCHK(hipMemcpyAsync(s->cg.phi_h.data(), s->cg.phi, (size_t)n_kept * S * 8, hipMemcpyDeviceToHost, st));
+    s->cg.phi_h.assign((size_t)n_kept * SQ, 0.0);
+    HIPCHK(hipMemcpyAsync(s->cg.phi_h.data(), s->cg.phi, (size_t)n_kept * SQ * 8, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     s->cg.iter = s->iter;
     s->cg.lo = k_lo;
     s->cg.n = n_kept;
   }
-  // 2. per subset: nodes over its kept phi range (a nearly fixed phi: a short interval around it)
-  const double pa = md.phi_a[0], pb = md.phi_b[0];
-  std::vector<double> lo(S), hi(S);
+  // 2. per pair: nodes over its kept phi range, inside its outcome's prior (a nearly fixed phi: a short
+  //    interval around it)
+  std::vector<double> lo(SQ), hi(SQ);
   long refreshes = 0;
-  for (int i = 0; i < S; ++i) {
+  for (int i = 0; i < SQ; ++i) {
+    const double pa = md.phi_a[i % q], pb = md.phi_b[i % q];
     double l = s->cg.phi_h[i], h = l;
     refreshes += 1;
     for (int j = 1; j < n_kept; ++j) {
-      const double v = s->cg.phi_h[(size_t)j * S + i];
-      refreshes += v != s->cg.phi_h[(size_t)(j - 1) * S + i];
+      const double v = s->cg.phi_h[(size_t)j * SQ + i];
+      refreshes += v != s->cg.phi_h[(size_t)(j - 1) * SQ + i];
       l = std::fmin(l, v);
       h = std::fmax(h, v);
     }
@@ -509,37 +536,39 @@ static int predict_tile_cheb(mk_session* s, int t0, double* dq, mk_outputs* o, d
   std::vector<double> wts;
   const int E = cheb_plan(s, lo, hi, force_n, MK_CHEB_CHECKS, nc, sphi, wts);
   long evals = 0;
-  for (int i = 0; i < S; ++i) evals += nc[i] + MK_CHEB_CHECKS;
-  // auto: only where it saves exact evaluations -- the exact replay refreshes X at each subset's first
-  // state and wherever phi changed (a short window, e.g. the bench's 6-state kriging sample, refreshes
-  // less often than a range needs nodes)
+  for (int i = 0; i < SQ; ++i) evals += nc[i] + MK_CHEB_CHECKS;
+  // auto: only where it saves exact evaluations, summed over the pairs -- the exact replay refreshes a
+  // pair's X at its first state and wherever its phi_h changed (a short window, e.g. the bench's 6-state
+  // kriging sample, refreshes less often than a range needs nodes)
   if (force_n == 1 && evals >= refreshes) return MK_CHEB_EXACT;
   // 3. g_k = W_k' z_k of the window's kept states (once per window): the exact replay's
   //    factorisations where phi changed, then one W' z per state
   const int nkp = (n_kept + 7) / 8 * 8;
   if (!s->cg.G) {
-    if (s->alloc(&s->cg.G, (size_t)S * n_pad * nkp)) return MK_CHEB_EXACT;
-    if (s->alloc(&s->cg.phit, (size_t)S * nkp)) {
+    if (s->alloc(&s->cg.G, (size_t)SQ * n_pad * nkp)) return MK_CHEB_EXACT;
+    if (s->alloc(&s->cg.phit, (size_t)SQ * nkp)) {
       s->release(s->cg.G);
       s->cg.G = nullptr;
       return MK_CHEB_EXACT;
     }
-    std::vector<double> pt((size_t)S * nkp);
-    for (int i = 0; i < S; ++i)
-      for (int j = 0; j < nkp; ++j) pt[(size_t)i * nkp + j] = s->cg.phi_h[(size_t)std::min(j, n_kept - 1) * S + i];
+    std::vector<double> pt((size_t)SQ * nkp);
+    for (int i = 0; i < SQ; ++i)
+      for (int j = 0; j < nkp; ++j) pt[(size_t)i * nkp + j] = s->cg.phi_h[(size_t)std::min(j, n_kept - 1) * SQ + i];
     HIPCHK(hipMemcpyAsync(s->cg.phit, pt.data(), pt.size() * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemsetAsync(s->cg.G, 0, (size_t)S * n_pad * nkp * 8, st));
+    HIPCHK(hipMemsetAsync(s->cg.G, 0, (size_t)SQ * n_pad * nkp * 8, st));
     Model mt = md;
     for (int j = 0; j < n_kept; ++j) {
       const int k = k_lo + j;
       mt.theta = md.kth + (long)k * S * nth;
       const double* prev = j ? md.kth + (long)(k - 1) * S * nth : nullptr;
       MK_LAUNCH(k_kept_dirty, dim3(1), dim3(256), 0, st, mt, prev, s->d_slist, s->d_scount, g.d_plist, g.d_pcount);
-      launch_candidates(mt, g.ms, st, S, 0, 1, 2, 0, s->d_slist, s->d_scount);
-      launch_cholesky(s, g, 0, 1, s->d_slist, s->d_scount);
-      MK_LAUNCH(k_flip_pairs, dim3((S + 255) / 256), dim3(256), 0, st, g.ms, g.d_plist, g.d_pcount);
-      launch_trinv(s, g, S, g.d_plist, g.d_pcount);
-      MK_LAUNCH(k_krig_g, dim3(S * (n_pad / 4)), dim3(256), 0, st, mt, g.ms, md.kz + (long)k * S * n_pad, s->cg.G,
+      for (int h = 0; h < q; ++h) {
+        launch_candidates(mt, g.ms, st, S, h, 1, 2, 0, s->d_slist + h * S, s->d_scount + h);
+        launch_cholesky(s, g, h, 1, s->d_slist + h * S, s->d_scount + h);
+      }
+      MK_LAUNCH(k_flip_pairs, dim3((SQ + 255) / 256), dim3(256), 0, st, g.ms, g.d_plist, g.d_pcount);
+      launch_trinv(s, g, SQ, g.d_plist, g.d_pcount);
+      MK_LAUNCH(k_krig_g, dim3(SQ * (n_pad / 4)), dim3(256), 0, st, mt, g.ms, md.kz + (long)k * SQ * n_pad, s->cg.G,
                 j, nkp);
       HIPCHK(hipGetLastError());
       // the host stays at most 32 states (~2,000 launches) ahead: rocprofv3's queue intercept read
@@ -569,7 +598,9 @@ static int predict_tile_cheb(mk_session* s, int t0, double* dq, mk_outputs* o, d
     return MK_CHEB_EXACT;
   }
   // 5. the draws
-  MK_LAUNCH(k_pred_cheb_draw, dim3(S * ((Tc + 255) / 256)), dim3(256), 0, st, mt, ck, s->cg.G, s->cg.phit, md.coords,
+  void (*k_pred_cheb_draw_q)(Model, ChebK, const double*, const double*, const double*, const double*, int, int) =
+      q == 1 ? k_pred_cheb_draw<1> : q == 2 ? k_pred_cheb_draw<2> : q == 3 ? k_pred_cheb_draw<3> : k_pred_cheb_draw<4>;
+  MK_LAUNCH(k_pred_cheb_draw_q, dim3(S * ((Tc + 255) / 256)), dim3(256), 0, st, mt, ck, s->cg.G, s->cg.phit, md.coords,
             md.kA, k_lo, nkp);
   HIPCHK(hipGetLastError());
   Stat& c = s->prof.stats[KS_KRIG_CHEB];

@@ -1910,9 +1910,11 @@ __global__ __launch_bounds__(256) void k_flip_pairs(MatSet ms, const int* __rest
 }
 
 // ---------------------------------------------------------------- 11. phi-interpolated tiled kriging
-// (exponential, q = 1; mk_api.hip predict_tile_cheb).  spPredict's draw for kept state k at test site t
-// is w*_k(t) = A_k (m_k(t) + sqrt(1 - s(t; phi_k)) e), with m_k(t) = rho_t(phi_k)' R(phi_k)^-1 u_k and
-// s(t; phi) = rho_t(phi)' R(phi)^-1 rho_t(phi).  The exact replay recomputes X = W P^T, i.e. s at every
+// (exponential, q <= MK_QMAX; mk_krig.hip predict_tile_cheb).  spPredict's draw for kept state k at test
+// site t is w*_k(t) = A_k (m_k(t) + sqrt(1 - s(t; phi_k)) e), with m_k(t) = rho_t(phi_k)' R(phi_k)^-1 u_k and
+// s(t; phi) = rho_t(phi)' R(phi)^-1 rho_t(phi) -- under the LMC per outcome h, each with its own phi_h, R_h,
+// u_h and normal, mixed by A_k afterwards; everything below is per (subset, outcome) pair sh = s q + h, and
+// the fused path's tables (q = 1) are the case sh = s.  The exact replay recomputes X = W P^T, i.e. s at every
 // phi the chain visited (0.39 refreshes per kept state at configs[4]).  s is an analytic function of
 // phi on the kept range: it is interpolated instead from exact values at Chebyshev nodes of that range
 // (barycentric form, nodes of the first kind), and every tile checks the interpolant against exact
@@ -1935,25 +1937,29 @@ __device__ inline double dist_fast(double x0, double y0, double x1, double y1) {
   return x > 0.0 ? g : 0.0;
 }
 
-// phis[j][s] = phi of record j (th: [n][S][n_theta] records): the candidate assembly's formula
-// (candidate_theta, which = 2), so a record's phi here is bit for bit the one its factor used.
+// phis[j][sh] = phi_h of record j (th: [n][S][n_theta] records), pair sh = s q + h: the candidate
+// assembly's formula (candidate_theta, which = 2) with outcome h's prior ends, so a record's phi here is
+// bit for bit the one its factor used.
 __global__ __launch_bounds__(256) void k_kept_phi(Model md, const double* __restrict__ th, int n,
                                                   double* __restrict__ phis) {
   const long e = (long)blockIdx.x * 256 + threadIdx.x;
-  if (e >= (long)n * md.S) return;
-  phis[e] = logit_inv(th[e * md.n_theta + md.ntri], md.phi_a[0], md.phi_b[0]);
+  if (e >= (long)n * md.S * md.q) return;
+  const long rec = e / md.q;
+  const int h = (int)(e - rec * md.q);
+  phis[e] = logit_inv(th[rec * md.n_theta + md.ntri + h], md.phi_a[h], md.phi_b[h]);
 }
 
-// g = W' z for every subset (q = 1): g_i = sum_{i <= r < n_s} W[r, i] z_r, one wave per column i
-// (W column-major: the wave's loads are contiguous); g_i = 0 for i >= n_s.  Stored state-minor,
-// Gt[s][i][j] (j: the window state, nkp per row), so a pass over 8 states reads 64 contiguous bytes.
+// g = W' z for every pair sh (grid: S q n_pad / 4; z: the state's [S][q][n_pad] record):
+// g_i = sum_{i <= r < n_s} W[r, i] z_r, one wave per column i (W column-major: the wave's loads are
+// contiguous); g_i = 0 for i >= n_s.  Stored state-minor, Gt[sh][i][j] (j: the window state, nkp per
+// row), so a pass over 8 states reads 64 contiguous bytes.
 __global__ __launch_bounds__(256) void k_krig_g(Model md, MatSet ms, const double* __restrict__ z,
                                                 double* __restrict__ Gt, int j, int nkp) {
   const int per = md.n_pad / 4;
-  const int s = blockIdx.x / per;
+  const int s = blockIdx.x / per;   // the pair
   const int i = (blockIdx.x % per) * 4 + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
-  const int ns = md.n_s[s];
+  const int ns = md.n_s[s / md.q];
   const long ld = ms.ld;
   const double* Wc = ms.W + (long)s * ld * ld + (long)i * ld;
   const double* zs = z + (long)s * md.n_pad;
@@ -1970,9 +1976,9 @@ __global__ __launch_bounds__(256) void k_krig_g(Model md, MatSet ms, const doubl
   if (lane == 0) Gt[((long)s * md.n_pad + i) * nkp + j] = (i < ns) ? acc : 0.0;
 }
 
-// s(t; phi) of subset s from its nodes (slots 0 .. nc-1): barycentric interpolation of the second
-// kind with the Chebyshev weights (-1)^i sin((2i + 1) pi / (2 nc)) (wts[s][i]); a node's own value
-// at its phi.
+// s(t; phi) of pair s (of S pairs) from its nodes (slots 0 .. nc-1): barycentric interpolation of the
+// second kind with the Chebyshev weights (-1)^i sin((2i + 1) pi / (2 nc)) (wts[s][i]); a node's own
+// value at its phi.
 __device__ inline double cheb_s(const ChebK& c, int S, int s, long t, double phi) {
   const int nc = c.nc[s];
   const double* w = c.wts + (long)s * MK_CHEB_MAX;
@@ -1989,21 +1995,22 @@ __device__ inline double cheb_s(const ChebK& c, int S, int s, long t, double phi
 }
 
 // The interpolant against the exact values at the check slots nc .. nc+nchk-1 (the range's ends, its
-// middle, its quarters): the largest |difference| over the tile's sites and subsets into *err (bit pattern of a
-// non-negative double; a NaN counts as +inf).
+// middle, its quarters): the largest |difference| over the tile's sites and pairs (grid: S q blocks of
+// sites) into *err (bit pattern of a non-negative double; a NaN counts as +inf).
 __global__ __launch_bounds__(256) void k_cheb_check(Model md, ChebK c, unsigned long long* err) {
   __shared__ double red[4];
   const int nb = (md.n_test + 255) / 256;
-  const int s = blockIdx.x / nb;
+  const int SQ = md.S * md.q;
+  const int s = blockIdx.x / nb;   // the pair
   const int t = (blockIdx.x % nb) * 256 + threadIdx.x;
   double e = 0.0;
   if (t < md.n_test) {
     const int nc = c.nc[s];
     for (int k = 0; k < c.nchk; ++k) {
       const int slot = nc + k;
-      const double phi = c.nphi[(long)slot * md.S + s];
-      const double ex = c.Sn[((long)slot * md.S + s) * c.T_pad + t];
-      const double d = fabs(cheb_s(c, md.S, s, t, phi) - ex);
+      const double phi = c.nphi[(long)slot * SQ + s];
+      const double ex = c.Sn[((long)slot * SQ + s) * c.T_pad + t];
+      const double d = fabs(cheb_s(c, SQ, s, t, phi) - ex);
       if (!(d <= e)) e = (d != d) ? INFINITY : d;
     }
   }
@@ -2020,10 +2027,15 @@ __global__ __launch_bounds__(256) void k_cheb_check(Model md, ChebK c, unsigned 
 // The draws of the window's kept states j = 0 .. md.n_kept-1 (state k = k_lo + j) at the tile's sites,
 // one thread per (subset, site), 8 states per pass over the subset's sites: the distance once per
 // site and pass (dist_fast), rho_t(phi) = exp(-phi d) once per distinct phi among the 8 (consecutive
-// states share phi while the chain stays), m_k(t) = sum_i rho_i g_k,i in site order (fma).  Gt [S][n_pad][nkp] and phit
-// [S][nkp] are zero / last-phi padded to nkp (a multiple of 8), and with the coordinates they are read
-// through scalar loads (uniform addresses).  The normal, the A factor and the output layout are
-// k_pred_draw_runs' (q = 1).
+// states share phi while the chain stays), m_k(t) = sum_i rho_i g_k,i in site order (fma).  Q outcomes:
+// the distance is shared, each outcome h has its own phi_h, exps, g (pair s Q + h) and 8 sums; the
+// normal of (site, h) is k_pred_draw's (index (t_off + t) Q + h), and so are the A mix (o = 0;
+// o += v[h] A[a + h Q], h ascending, A the state's Q x Q record of kA) and the output layout
+// ([S][n_kept][n_test Q], outcome-minor).  Gt [S Q][n_pad][nkp] and phit [S Q][nkp] are zero / last-phi
+// padded to nkp (a multiple of 8), and with the coordinates and A they are read through scalar loads
+// (uniform addresses).  Every loop over Q and the 8 states is unrolled, so p, a, sd and v are indexed
+// at compile time only (registers, no scratch).  Q = 1 is the arithmetic of k_pred_draw_runs' draw.
+template <int Q>
 __global__ __launch_bounds__(256) void k_pred_cheb_draw(Model md, ChebK c, const double* __restrict__ Gt,
                                                         const double* __restrict__ phit,
                                                         const double* __restrict__ coords,
@@ -2037,41 +2049,68 @@ __global__ __launch_bounds__(256) void k_pred_cheb_draw(Model md, ChebK c, const
   const double xt = md.coords_test[t], yt = md.coords_test[md.n_test_pad + t];
   const double* cx = coords + (long)s * 2 * np;
   const double* cy = cx + np;
-  const double* ph = phit + (long)s * nkp;
-  const double* gs = Gt + (long)s * np * nkp;
+  const double* ph = phit + (long)s * Q * nkp;
+  const double* gs = Gt + (long)s * Q * np * nkp;
   const Key key = subset_key(md, s);
   for (int j0 = 0; j0 < n; j0 += 8) {
-    double p[8];
+    double p[Q][8];
 #pragma unroll
-    for (int b = 0; b < 8; ++b) p[b] = ph[j0 + b];
-    double a[8];
+    for (int h = 0; h < Q; ++h)
 #pragma unroll
-    for (int b = 0; b < 8; ++b) a[b] = 0.0;
+      for (int b = 0; b < 8; ++b) p[h][b] = ph[(long)h * nkp + j0 + b];
+    double a[Q][8];
+#pragma unroll
+    for (int h = 0; h < Q; ++h)
+#pragma unroll
+      for (int b = 0; b < 8; ++b) a[h][b] = 0.0;
 #pragma unroll 2
     for (int i = 0; i < ns; ++i) {
       const double d = dist_fast(cx[i], cy[i], xt, yt);
-      const double* gi = gs + (long)i * nkp + j0;
-      double e = exp(-p[0] * d);
-      a[0] = fma(e, gi[0], a[0]);
 #pragma unroll
-      for (int b = 1; b < 8; ++b) {
-        if (p[b] != p[b - 1]) e = exp(-p[b] * d);
-        a[b] = fma(e, gi[b], a[b]);
+      for (int h = 0; h < Q; ++h) {
+        const double* gi = gs + ((long)h * np + i) * nkp + j0;
+        double e = exp(-p[h][0] * d);
+        a[h][0] = fma(e, gi[0], a[h][0]);
+#pragma unroll
+        for (int b = 1; b < 8; ++b) {
+          if (p[h][b] != p[h][b - 1]) e = exp(-p[h][b] * d);
+          a[h][b] = fma(e, gi[b], a[h][b]);
+        }
       }
     }
-    double sd = 0.0;
+    double sd[Q];
+#pragma unroll
+    for (int h = 0; h < Q; ++h) sd[h] = 0.0;
 #pragma unroll
     for (int b = 0; b < 8; ++b) {
       if (j0 + b >= n) break;
-      if (b == 0 || p[b] != p[b - 1]) sd = sqrt(fmax(1.0 - cheb_s(c, S, s, t, p[b]), 0.0));
       const int k = k_lo + j0 + b;
-      const double v = a[b] + sd * predict_normal(key, md.t_off + t, md.kept0 + k);
-      double o = 0.0;
-      o += v * kA[(long)k * S + s];
-      if (act) md.w_pred[((long)s * n + j0 + b) * md.n_test + t] = o;
+      double v[Q];
+#pragma unroll
+      for (int h = 0; h < Q; ++h) {
+        if (b == 0 || p[h][b] != p[h][b - 1]) sd[h] = sqrt(fmax(1.0 - cheb_s(c, S * Q, s * Q + h, t, p[h][b]), 0.0));
+        v[h] = a[h][b] + sd[h] * predict_normal(key, (md.t_off + t) * Q + h, md.kept0 + k);
+      }
+      const double* A = kA + ((long)k * S + s) * (Q * Q);
+      double* out = md.w_pred + ((long)s * n + j0 + b) * Q * md.n_test + (long)t * Q;
+#pragma unroll
+      for (int r = 0; r < Q; ++r) {
+        double o = 0.0;
+#pragma unroll
+        for (int h = 0; h < Q; ++h) o += v[h] * A[r + h * Q];
+        if (act) out[r] = o;
+      }
     }
   }
 }
+template __global__ void k_pred_cheb_draw<1>(Model, ChebK, const double*, const double*, const double*, const double*,
+                                             int, int);
+template __global__ void k_pred_cheb_draw<2>(Model, ChebK, const double*, const double*, const double*, const double*,
+                                             int, int);
+template __global__ void k_pred_cheb_draw<3>(Model, ChebK, const double*, const double*, const double*, const double*,
+                                             int, int);
+template __global__ void k_pred_cheb_draw<4>(Model, ChebK, const double*, const double*, const double*, const double*,
+                                             int, int);
 
 // Fused kriging from the session's phi tables (mk_api.hip krig_tables; q = 1): what a kept iteration's
 // draws read, captured after its sweep (z, phi, A), so they can run on a side stream while the next

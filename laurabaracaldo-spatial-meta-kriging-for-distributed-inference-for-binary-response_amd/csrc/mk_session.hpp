@@ -62,9 +62,9 @@ enum { KS_CHOL_UPDATE = 0, KS_CHOL_DIAG, KS_CHOL_TRSM, KS_SWEEP, KS_LAUUM, KS_IT
        KS_UPDATE_BUSY, KS_PRED_VAR, KS_COV, KS_SWEEP_FALLBACK, KS_KRIG_CHEB, KS_KRIG_FALLBACK, KS_DIAG, KS_CRIT,
        KS_SCORE, KS_MAPS };
 // KS_KRIG_CHEB: tiles kriged by phi interpolation (predict_tile_cheb): launches = tiles, flops = exact
-// s evaluations ((subset, node or check point) pairs), total_ms = the largest check difference seen
-// (not a time).  KS_KRIG_FALLBACK: tiles whose check failed and were replayed exactly (launches), and
-// total_ms the largest failing difference.
+// s evaluations (one per (subset, outcome) pair and node or check point), total_ms = the largest check
+// difference seen over all pairs and sites (not a time).  KS_KRIG_FALLBACK: tiles whose check failed
+// and were replayed exactly (launches), and total_ms the largest failing difference.
 // KS_DIAG: the chain-diagnostic launches (k_chain_diag, k_chain_diag_prob), bracketed by events whether
 // or not the profiler is on (a handful per call, each followed by a wait anyway).
 // KS_CRIT: the model-assessment launches (k_crit_accum per kept iteration and stream group, k_crit_replay,
@@ -178,11 +178,12 @@ struct KrigTables {
 };
 
 // mk_krig.hip (predict_tile_cheb).  Phi-interpolated tiled kriging: the window's g_k = W_k' z_k and
-// phi_k, kept across tiles (made at the first tile after a run or a window change).
+// phi_k per (subset, outcome) pair, kept across tiles (made at the first tile after a run or a window
+// change).
 struct ChebWindow {
-  double* G = nullptr;         // [S][n_pad][nkp]: g of the window's states (nkp = window rounded up to 8)
-  double* phi = nullptr;       // [win][S]
-  double* phit = nullptr;      // [S][nkp]: phi per state, padded with the last
+  double* G = nullptr;         // [S q][n_pad][nkp]: g of the window's states (nkp = window rounded up to 8)
+  double* phi = nullptr;       // [win][S q]
+  double* phit = nullptr;      // [S q][nkp]: phi per state, padded with the last
   std::vector<double> phi_h;
   int iter = -1, lo = -1, n = -1;
 };

@@ -110,16 +110,17 @@ struct MatSet {
   int ld, nt, q;
 };
 
-// phi-interpolated tiled kriging (mk_mcmc.hip section 11, mk_api.hip predict_tile_cheb)
-#define MK_CHEB_MAX 32      // Chebyshev nodes per subset at most
-#define MK_CHEB_CHECKS 3    // exact check values per subset and tile: the kept range's ends and middle
+// phi-interpolated kriging (mk_mcmc.hip section 11, mk_krig.hip predict_tile_cheb / krig_tables); every
+// array is per (subset, outcome) pair sh = s q + h, SQ = S q of them (the fused tables: q = 1)
+#define MK_CHEB_MAX 32      // Chebyshev nodes per pair at most
+#define MK_CHEB_CHECKS 3    // exact check values per pair and tile: the kept range's ends and middle
 #define MK_CHEB_CHECKS_MAX 5
 struct ChebK {
-  const double* Sn;     // [slot][S][T_pad]  exact s at the nodes (slots < nc[s]) and the check points
-  const double* nphi;   // [slot][S]         the slots' phi (as the candidate assembly computed it)
-  const double* wts;    // [S][MK_CHEB_MAX]  barycentric weights
-  const int* nc;        // [S]               nodes
-  int nchk;             // check slots per subset (after the nodes)
+  const double* Sn;     // [slot][SQ][T_pad]  exact s at the nodes (slots < nc[sh]) and the check points
+  const double* nphi;   // [slot][SQ]         the slots' phi (as the candidate assembly computed it)
+  const double* wts;    // [SQ][MK_CHEB_MAX]  barycentric weights
+  const int* nc;        // [SQ]               nodes
+  int nchk;             // check slots per pair (after the nodes)
   long T_pad;
 };
 

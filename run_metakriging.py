@@ -228,6 +228,14 @@ def main():
                   file=sys.stderr, flush=True)
     if a.validate and world == 1 and big:
         scores = ses.scores()                     # every tile has been replayed
+    krig = None
+    if ses is not None and big:                   # how this shard's tiles were kriged (any q)
+        cheb, fb = (ses.kernel_stats(k) for k in (mk.session.KS_KRIG_CHEB, mk.session.KS_KRIG_FALLBACK))
+        n_int = cheb["launches"]
+        krig = {"mode": os.environ.get("MK_KRIG_CHEB", "1"), "tile": int(tile),
+                "interpolated_tiles": n_int, "fallback_tiles": fb["launches"],
+                "exact_evaluations_per_pair_and_tile": cheb["flops"] / (n_int * len(subs) * q) if n_int else None,
+                "max_check_difference": cheb["ms"] if n_int else None}
     if ses is not None:
         ses.close()
     t["combine_s"] = time.perf_counter() - t4
@@ -249,6 +257,8 @@ def main():
             rec["w_test_coverage_95"] = float(np.mean((d["w_test_true"] >= wq[1]) & (d["w_test_true"] <= wq[2])))
             rec["truth_beta_phi"] = truth.tolist()
             rec.update(predictive_scores(result3, d))
+        if krig is not None:
+            rec["kriging_replay"] = krig
         print(json.dumps(rec), flush=True)
         if a.diagnostics:
             print(json.dumps({"diagnostics": mk.convergence_report(diag)}), flush=True)
