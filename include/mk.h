@@ -201,7 +201,8 @@ int mk_session_tile_grids_wp(mk_session* s, int32_t t0, double* out_w, double* o
  * ms, always timed, 0 launches unless criteria were asked for; 16 the held-out scoring launches
  * k_score_cols / k_score_finish -- launches and ms, always timed, 0 launches unless validation data were
  * attached; 17 the posterior-map launches k_map_cols -- launches and ms, always timed, 0 launches unless
- * maps were asked for).  Flops are algorithmic, not executed: GEMM tiles 2 m n k, the diagonal tile's
+ * maps were asked for; 18 the cross-outcome launches k_quantiles_pair / k_pair_cols -- launches (one per
+ * kernel) and ms, always timed, 0 launches unless pairs were asked for).  Flops are algorithmic, not executed: GEMM tiles 2 m n k, the diagonal tile's
  * update as a SYRK, solves and inverse products over their triangles.  mk_session_profile(s, enable)
  * before mk_session_run: enable 0 = off, 1 = every kind, otherwise a mask with bit (1 + kind) per kind
  * bracketed (e.g. 2 << 0 = the panel update only; fewer events, less overhead). */
@@ -478,6 +479,70 @@ int mk_meta_fit_maps(const mk_problem* prob, const mk_config* cfg, const int32_t
                      mk_progress_fn progress, void* user, mk_outputs* out, mk_combined* comb, mk_diagnostics* diag,
                      mk_criteria* crit, const mk_validation* val, mk_scores* scores, const mk_map_spec* spec,
                      mk_maps* maps);
+
+/* ---- cross-outcome prediction (q >= 2): co-occurrence and contrast of two outcomes at a test site ----
+ * A kept state's kriging draws at a site are joint across the q outcomes (w* = A (m + diag(sd) z)), so
+ * functionals of two outcomes at ONE site have a posterior the per-column outputs cannot give.  (Across
+ * sites the draws are marginal by design: nothing here aggregates over sites.)
+ * Pairs (a, b), a < b, are numbered r = 0 .. n_pairs - 1 in the order
+ *   for a in 0 .. q-2: for b in a+1 .. q-1
+ * so n_pairs = q (q - 1) / 2 (at most 6).  Pair column e = t n_pairs + r for test site t (site-major, as
+ * the columns are location-major); C2 = n_pairs n_test.
+ * Each subset on its own; k = 1..n the kept states of the window in time order; p_a,k and p_b,k are
+ * pred_prob's values of columns t q + a and t q + b: the p_pred_samples bit for bit.
+ *   both_k = p_a,k * p_b,k   P(y_a = 1, y_b = 1 | state) -- the outcomes are conditionally independent given
+ *                            eta.  One fp64 multiplication, never contracted into a neighbouring add, so
+ *                            the planes and the grids see the same numbers
+ *   diff_k = p_a,k - p_b,k
+ * Grids: both_predict and diff_predict, each 200 x C2 column-major per subset: the type-7 quantiles of the
+ * draws above at the 200 levels, laid out as p_predict is.
+ * Planes per subset: MK_N_PAIR_BASE + J, C2 x (6 + J) column-major, in the order
+ *   both_mean, both_sd, diff_mean, diff_sd, corr, a_gt_b, joint_1..joint_J
+ *   means    (sum_k v_k) / n, summed in time order from zero
+ *   sds      the maps' Welford recurrence; NaN when n = 1
+ *   corr     the posterior correlation of (p_a, p_b): beside the two marginal Welford pairs (m, M2) the
+ *            co-moment C = C + (p_a - m_a,old) (p_b - m_b,new); corr = C / (sqrt(M2_a) sqrt(M2_b)), NaN when
+ *            either M2 is 0 or n < 2
+ *   a_gt_b   #{k : p_a,k > p_b,k} / n, strict
+ *   joint_j  #{k : p_a,k > u_j and p_b,k > u_j} / n, strict ("both above 20 %"); the thresholds are checked as
+ *            the maps' are: finite, J <= MK_MAP_MAXT
+ * A non-finite draw or eta in either column makes every plane of the pair NaN.
+ * The combined grids combined_both / combined_diff (200 x C2) are the K subsets' grids combined by
+ * mk_combined.method (mean or median; the mean when comb is NULL).  Their planes are mk_map_grid's: of
+ * combined_both with the thresholds, of combined_diff with the one threshold 0, whose exceedance column
+ * P(diff > 0) is the combined counterpart of a_gt_b.  A combined corr and a combined joint_j do not exist:
+ * the grids do not carry them. */
+#define MK_N_PAIR_BASE 6  /* planes before joint_1..J */
+typedef struct mk_pair_spec { int32_t n_thresholds; const double* thresholds; } mk_pair_spec;
+typedef struct mk_pairs {             /* caller-allocated, any pointer may be NULL */
+  double* both_predict;        /* [n_subsets] x (200 x C2) */
+  double* diff_predict;        /* [n_subsets] x (200 x C2) */
+  double* planes;              /* [n_subsets] x (C2 x (6 + J)) */
+  double* combined_both;       /* 200 x C2 (node call only) */
+  double* combined_diff;       /* 200 x C2 (node call only) */
+} mk_pairs;
+/* Ask the session for the pair outputs at its current test sites (NULL detaches and frees).  MK_E_ARG for
+ * q = 1, no test sites, no x_test or no recorded samples, and for a bad threshold (as mk_session_set_maps),
+ * all before any device is touched.  A tiled session takes its buffers here and only here: 3200 bytes of
+ * grids and 8 (6 + J) bytes of planes per (subset, pair column); MK_E_NOMEM names the remedies.  While
+ * attached, every tile replay of a tiled session also fills that tile's pair columns, from the same
+ * replay and over its kept window.  mk_session_set_test_sites detaches.  Nothing is launched or allocated
+ * for the pairs unless they were asked for. */
+int mk_session_set_pairs(mk_session* s, const mk_pair_spec* spec);
+/* After all iterations.  A fused session makes what is asked for from its kriging draws (all kept states)
+ * now, in scratch held for the call.  A tiled session copies its buffers out: MK_E_ARG, naming the first
+ * such tile, if some tile has not been replayed over the current kept window since the pairs were
+ * attached.  combined_both / combined_diff are not written here. */
+int mk_session_pairs(mk_session* s, mk_pairs* out);
+/* mk_meta_fit_maps with the pair outputs (mk_meta_fit_maps is this call with two NULLs): every block
+ * attaches the spec and writes its subsets' grids and planes at their global offsets into the caller's
+ * arrays (into a host scratch when only a combined grid is asked for); the calling thread then combines the
+ * host copies with mk_combine / mk_combine_median.  Nothing is added to the exchange; the host holds
+ * K 200 C2 8 bytes per functional (0.27 GB at 56 subsets x 3 pairs x 1,000 sites). */
+int mk_meta_fit_pairs(const mk_problem* prob, const mk_config* cfg, const int32_t* devices, int32_t n_devices,
+                      mk_progress_fn progress, void* user, mk_outputs* out, mk_combined* comb, mk_diagnostics* diag,
+                      mk_criteria* crit, const mk_validation* val, mk_scores* scores, const mk_map_spec* spec,
+                      mk_maps* maps, const mk_pair_spec* pair_spec, mk_pairs* pairs);
 
 /* ---- combine (MK.R:123-133): out = (grid_1 + ... + grid_K) / K, sequential order ---- */
 int mk_combine(const double* grids, int32_t K, int64_t grid_len, double* out, int32_t device);

@@ -32,6 +32,8 @@ SCORE_NAMES = ["n", "lpd", "brier", "err", "lconst"]
 MAP_MAXT = 8           # MK_MAP_MAXT: exceedance thresholds at most
 N_MAP_BASE = 4         # MK_N_MAP_BASE: the planes before the exceedances, in MAP_BASE_NAMES' order
 MAP_BASE_NAMES = ["w_mean", "w_sd", "p_mean", "p_sd"]
+N_PAIR_BASE = 6        # MK_N_PAIR_BASE: the pair planes before joint_1..J, in PAIR_BASE_NAMES' order
+PAIR_BASE_NAMES = ["both_mean", "both_sd", "diff_mean", "diff_sd", "corr", "a_gt_b"]
 
 _dp = ctypes.POINTER(ctypes.c_double)
 _ip = ctypes.POINTER(ctypes.c_int32)
@@ -104,6 +106,15 @@ class Maps(ctypes.Structure):
     _fields_ = [("subsets", _dp), ("combined", _dp)]
 
 
+class PairSpec(ctypes.Structure):
+    _fields_ = [("n_thresholds", ctypes.c_int32), ("thresholds", _dp)]
+
+
+class Pairs(ctypes.Structure):
+    _fields_ = [("both_predict", _dp), ("diff_predict", _dp), ("planes", _dp), ("combined_both", _dp),
+                ("combined_diff", _dp)]
+
+
 # int (*mk_progress_fn)(void* user, int32_t iterations, int32_t n_samples)
 PROGRESS_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32)
 
@@ -119,6 +130,13 @@ EXPORTS = {
                                         PROGRESS_FN, ctypes.c_void_p, ctypes.POINTER(Outputs), ctypes.POINTER(Combined),
                                         ctypes.POINTER(Diagnostics), ctypes.POINTER(Criteria), ctypes.POINTER(Validation),
                                         ctypes.POINTER(Scores), ctypes.POINTER(MapSpec), ctypes.POINTER(Maps)]),
+    "mk_meta_fit_pairs": (ctypes.c_int, [ctypes.POINTER(Problem), ctypes.POINTER(Config), _ip, ctypes.c_int32,
+                                         PROGRESS_FN, ctypes.c_void_p, ctypes.POINTER(Outputs), ctypes.POINTER(Combined),
+                                         ctypes.POINTER(Diagnostics), ctypes.POINTER(Criteria), ctypes.POINTER(Validation),
+                                         ctypes.POINTER(Scores), ctypes.POINTER(MapSpec), ctypes.POINTER(Maps),
+                                         ctypes.POINTER(PairSpec), ctypes.POINTER(Pairs)]),
+    "mk_session_set_pairs": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(PairSpec)]),
+    "mk_session_pairs": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(Pairs)]),
     "mk_session_set_maps": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(MapSpec)]),
     "mk_session_maps": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(Maps)]),
     "mk_map_grid": (ctypes.c_int, [_dp, ctypes.c_int32, ctypes.c_int64, _dp, ctypes.c_int32, _dp, ctypes.c_int32]),

@@ -142,4 +142,45 @@ __device__ inline double block_sum(double v, double* red) {
   return red[NT / 64];
 }
 
+// State k (1-based) with value v into a running sum and a Welford pair (k_map_cols, k_pair_cols).
+__device__ inline void map_update(double& sum, double& m, double& M2, double v, double k) {
+  sum = sum + v;
+  const double d = v - m;
+  m = m + d / k;
+  M2 = M2 + d * (v - m);
+}
+
+// The quantile kernels' LDS length: the next power of two >= n_rows.
+__device__ inline int quant_pow2(int n_rows) {
+  int n2 = 1;
+  while (n2 < n_rows) n2 <<= 1;
+  return n2;
+}
+
+// v[0 .. n2) filled (padding +INFINITY) and a barrier passed: sorts ascending, then writes the
+// n_probs type-7 quantiles of the first n_rows values to o.  256 threads.
+__device__ inline void quant_sort_readout(double* v, int n2, int n_rows, const double* __restrict__ probs, int n_probs,
+                                          double* __restrict__ o) {
+  for (int size = 2; size <= n2; size <<= 1) {
+    for (int stride = size >> 1; stride > 0; stride >>= 1) {
+      for (int t = threadIdx.x; t < n2 / 2; t += 256) {
+        const int lo = 2 * t - (t & (stride - 1));
+        const int hi = lo + stride;
+        const bool up = ((lo & size) == 0);
+        const double a = v[lo], b = v[hi];
+        if ((a > b) == up) { v[lo] = b; v[hi] = a; }
+      }
+      __syncthreads();
+    }
+  }
+  for (int l = threadIdx.x; l < n_probs; l += 256) {
+    const double index = 1.0 + (double)(n_rows - 1) * probs[l];
+    const double flo = floor(index), fhi = ceil(index);
+    const int lo = (int)flo, hi = (int)fhi;
+    const double qlo = v[lo - 1], qhi = v[hi - 1];
+    const double hh = index - flo;
+    o[l] = (index > flo && qhi != qlo) ? (1.0 - hh) * qlo + hh * qhi : qlo;
+  }
+}
+
 }  // namespace mk

@@ -24,6 +24,8 @@ int session_tile_grids(mk_session* s, int t0, double* d_out, mk_outputs* o, doub
 // mk_maps.hip: MK_E_ARG naming the index of a non-finite threshold, or J when it is outside 0 .. MK_MAP_MAXT;
 // touches no device.
 int map_spec_check(const double* thresholds, int J);
+// mk_pairs.hip: the checks of a pair spec that need no device -- the thresholds as above, and q >= 2.
+int pair_spec_check(const mk_pair_spec* spec, int q);
 hipError_t stream_acquire(int device, hipStream_t* st);
 void stream_release(int device, hipStream_t st);
 

@@ -140,6 +140,11 @@ __global__ void k_score_finish(const double* pw, const double* y, const double* 
 template <bool GRID>
 __global__ void k_map_cols(const double* data, long subset_stride, long row_stride, long col_stride, int n, int n_cols,
                            ProbSrc ps, MapThr th, long col0, long C, double* planes);
+// mk_pairs.hip
+__global__ void k_quantiles_pair(const double* data, long subset_stride, long row_stride, int n_rows, int n_pc, int q,
+                                 const double* probs, int n_probs, ProbSrc ps, long col0, long C2, double* out);
+__global__ void k_pair_cols(const double* data, long subset_stride, long row_stride, int n, int n_pc, int q, ProbSrc ps,
+                            MapThr th, long col0, long C2, double* planes);
 // mk_post.hip
 __global__ void k_weiszfeld(const double* grids, int K, int L, long C, int max_iter, double tol, double* out, int* iters);
 __global__ void k_post_index(uint64_t seed, int samplesize, int n_levels, int* idx);

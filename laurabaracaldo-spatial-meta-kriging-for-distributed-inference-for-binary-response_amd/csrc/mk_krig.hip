@@ -115,6 +115,7 @@ extern "C" int mk_session_set_test_sites(mk_session* s, int32_t n_test, const do
   s->diag_sink = mk_diagnostics{};
   validation_detach(s);                    // held-out data belonged to the sites that go
   maps_detach(s);                          // and the maps' planes were sized for them
+  pairs_detach(s);                         // so were the pair grids and planes
   int rc = set_test_covars(s, nullptr);   // the covariates belonged to the sites that go
   if (rc) return rc;
   return kriging_buffers(s, n_test, coords_test);
@@ -232,6 +233,11 @@ static int tile_outputs(mk_session* s, int t0, double* dq, double* dqp, mk_outpu
   // maps asked for: this tile's columns of the planes, from the same draws
   if (s->maps.on) {
     const int rc = tile_maps(s, t0, n_kept, Ct);
+    if (rc) return rc;
+  }
+  // pairs asked for: this tile's pair columns of the grids and planes, from the same draws
+  if (s->pairs.on) {
+    const int rc = tile_pairs(s, t0, n_kept, Ct);
     if (rc) return rc;
   }
   HIPCHK(hipStreamSynchronize(st));

@@ -21,14 +21,6 @@
 
 namespace mk {
 
-// State k (1-based) with value v into the running sum and the Welford pair.
-__device__ inline void map_update(double& sum, double& m, double& M2, double v, double k) {
-  sum = sum + v;
-  const double d = v - m;
-  m = m + d / k;
-  M2 = M2 + d * (v - m);
-}
-
 // Grid (ceil(n_cols / 256), S).  State k of column c of subset s is data[s * subset_stride + k * row_stride +
 // c * col_stride], as k_score_cols addresses it.  planes: [S][NB + J][C] with NB = 4 (session form: w_mean,
 // w_sd, p_mean, p_sd) or 2 (grid form: mean, sd), then exc_1..J; the column is col0 + c of them.

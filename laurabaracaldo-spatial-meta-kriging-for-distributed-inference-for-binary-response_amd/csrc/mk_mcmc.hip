@@ -1585,38 +1585,8 @@ __global__ __launch_bounds__(256) void k_run_start(const int* __restrict__ plist
 // power of two >= n_rows doubles, at most MK_QUANT_MAX = 128 KB), then R's quantile.default type 7:
 // (1-h) x[lo] + h x[hi] (no FMA contraction).  k_quantiles sorts the values as stored;
 // k_quantiles_prob sorts pred_prob of them (the transform is applied as LDS is filled, so the
-// probabilities of a [S][kept][C] draw buffer never exist in memory).
-__device__ inline int quant_pow2(int n_rows) {
-  int n2 = 1;
-  while (n2 < n_rows) n2 <<= 1;
-  return n2;
-}
-
-// v[0 .. n2) filled (padding +INFINITY) and a barrier passed: sorts ascending, then writes the
-// n_probs type-7 quantiles of the first n_rows values to o.  256 threads.
-__device__ inline void quant_sort_readout(double* v, int n2, int n_rows, const double* __restrict__ probs, int n_probs,
-                                          double* __restrict__ o) {
-  for (int size = 2; size <= n2; size <<= 1) {
-    for (int stride = size >> 1; stride > 0; stride >>= 1) {
-      for (int t = threadIdx.x; t < n2 / 2; t += 256) {
-        const int lo = 2 * t - (t & (stride - 1));
-        const int hi = lo + stride;
-        const bool up = ((lo & size) == 0);
-        const double a = v[lo], b = v[hi];
-        if ((a > b) == up) { v[lo] = b; v[hi] = a; }
-      }
-      __syncthreads();
-    }
-  }
-  for (int l = threadIdx.x; l < n_probs; l += 256) {
-    const double index = 1.0 + (double)(n_rows - 1) * probs[l];
-    const double flo = floor(index), fhi = ceil(index);
-    const int lo = (int)flo, hi = (int)fhi;
-    const double qlo = v[lo - 1], qhi = v[hi - 1];
-    const double hh = index - flo;
-    o[l] = (index > flo && qhi != qlo) ? (1.0 - hh) * qlo + hh * qhi : qlo;
-  }
-}
+// probabilities of a [S][kept][C] draw buffer never exist in memory).  quant_pow2 and
+// quant_sort_readout are in mk_common.hpp: k_quantiles_pair (mk_pairs.hip) sorts with them too.
 
 __global__ __launch_bounds__(256) void k_quantiles(const double* __restrict__ data, long subset_stride, long row_stride,
                                                    int n_rows, int n_cols, const double* __restrict__ probs, int n_probs,

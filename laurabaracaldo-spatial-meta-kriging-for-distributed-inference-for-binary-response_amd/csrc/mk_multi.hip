@@ -416,6 +416,14 @@ extern "C" int mk_meta_fit_maps(const mk_problem* pr, const mk_config* c, const 
                                 mk_progress_fn progress, void* user, mk_outputs* out, mk_combined* comb,
                                 mk_diagnostics* diag, mk_criteria* crit, const mk_validation* val, mk_scores* scores,
                                 const mk_map_spec* spec, mk_maps* maps) {
+  return mk_meta_fit_pairs(pr, c, devices, G, progress, user, out, comb, diag, crit, val, scores, spec, maps, nullptr,
+                           nullptr);
+}
+
+extern "C" int mk_meta_fit_pairs(const mk_problem* pr, const mk_config* c, const int32_t* devices, int32_t G,
+                                 mk_progress_fn progress, void* user, mk_outputs* out, mk_combined* comb,
+                                 mk_diagnostics* diag, mk_criteria* crit, const mk_validation* val, mk_scores* scores,
+                                 const mk_map_spec* spec, mk_maps* maps, const mk_pair_spec* pspec, mk_pairs* pairs) {
   if (!pr || !c) return fail(MK_E_ARG, "null problem/config");
   if (!devices || G < 1) return fail(MK_E_ARG, "n_devices must be >= 1 with a device list");
   const int K = pr->n_subsets;
@@ -431,6 +439,14 @@ extern "C" int mk_meta_fit_maps(const mk_problem* pr, const mk_config* c, const 
     const int e = map_spec_check(spec->thresholds, spec->n_thresholds);
     if (e) return e;
     J = spec->n_thresholds;
+  }
+  // cross-outcome prediction: per-subset outputs, and the grids the combined ones are made of
+  const bool pr_both = pairs && (pairs->both_predict || pairs->combined_both);
+  const bool pr_diff = pairs && (pairs->diff_predict || pairs->combined_diff);
+  const bool pr_any = pr_both || pr_diff || (pairs && pairs->planes);
+  if (pr_any) {   // the spec and q, before any device is touched
+    const int e = pair_spec_check(pspec, pr->q);
+    if (e) return e;
   }
   ApiCall call(__func__);
   DeviceGuard dg;   // the caller's current device is restored on every return path
@@ -458,6 +474,8 @@ extern "C" int mk_meta_fit_maps(const mk_problem* pr, const mk_config* c, const 
     return fail(MK_E_ARG, "posterior maps need test sites and x_test");
   if (mp_comb && !(comb && comb->result2 && comb->result3))
     return fail(MK_E_ARG, "the combined maps are those of comb->result2 (w) and comb->result3 (p): ask for both");
+  if (pr_any && (!pr->x_test || pr->n_test < 1))
+    return fail(MK_E_ARG, "cross-outcome prediction needs test sites and x_test");
   const int q = pr->q, p = pr->p, n_samples = c->n_batch * c->batch_length;
   if (c->n_batch < 1 || c->batch_length < 1) return fail(MK_E_ARG, "n.batch and batch.length must be >= 1");
 
@@ -503,7 +521,8 @@ extern "C" int mk_meta_fit_maps(const mk_problem* pr, const mk_config* c, const 
     int e = mk_session_create(&sp, &sc, &x.ses);
     if (e || (want_crit && (e = mk_session_set_criteria(x.ses, 1)))) return e;
     if (sc_sub && (e = mk_session_set_validation(x.ses, val))) return e;
-    return mp_sub ? mk_session_set_maps(x.ses, spec) : 0;
+    if (mp_sub && (e = mk_session_set_maps(x.ses, spec))) return e;
+    return pr_any ? mk_session_set_pairs(x.ses, pspec) : 0;
   });
   if (rc) return rc;
   if (nd.use_rccl) {
@@ -663,7 +682,7 @@ extern "C" int mk_meta_fit_maps(const mk_problem* pr, const mk_config* c, const 
     const PredKind pk{GRID_P, out ? out->p_predict : nullptr, out ? out->p_predict_sum : nullptr,
                       comb ? comb->result3 : nullptr, &Block::grids_p};
     const bool draws = out && (out->w_pred_samples || out->p_pred_samples);
-    const bool replay = tiled && (w.asked() || pk.asked() || draws || dg_w || dg_p || sc_sub || mp_sub);   // one replay per tile serves them all
+    const bool replay = tiled && (w.asked() || pk.asked() || draws || dg_w || dg_p || sc_sub || mp_sub || pr_any);   // one replay per tile serves them all
     if (!tiled) {
       for (const PredKind* k : {&pk, &w})   // p before w
         if (k->asked() && (rc = whole_grids(k->kind, C, k->h_each, k->h_comb, k->h_sum))) return rc;
@@ -735,6 +754,42 @@ extern "C" int mk_meta_fit_maps(const mk_problem* pr, const mk_config* c, const 
   if (mp_comb && ((rc = mk_map_grid(comb->result2, L, C, nullptr, 0, maps->combined, devices[0])) ||
                   (rc = mk_map_grid(comb->result3, L, C, spec->thresholds, J, maps->combined + 2 * (size_t)C, devices[0]))))
     return rc;
+  // ---- cross-outcome prediction (optional): the blocks' grids and planes at their global offsets -- a
+  // fused block makes them now, a tiled one was filled by the tile replays above; the combined grids from
+  // the host copies of all K (the caller's arrays, or a scratch when only the combined grid is asked for)
+  if (pr_any) {
+    const int np = q * (q - 1) / 2;
+    const size_t Gp = (size_t)np * n_test * L;
+    std::vector<double> keep_both, keep_diff;
+    double* h_both = pairs->both_predict;
+    double* h_diff = pairs->diff_predict;
+    if (pr_both && !h_both) {
+      keep_both.resize((size_t)K * Gp);
+      h_both = keep_both.data();
+    }
+    if (pr_diff && !h_diff) {
+      keep_diff.resize((size_t)K * Gp);
+      h_diff = keep_diff.data();
+    }
+    rc = nd.pool->run([&](int r) -> int {
+      Block& x = *nd.b[r];
+      if (!x.ses) return 0;
+      mk_pairs m{};
+      if (h_both) m.both_predict = h_both + (size_t)x.lo * Gp;
+      if (h_diff) m.diff_predict = h_diff + (size_t)x.lo * Gp;
+      if (pairs->planes) m.planes = pairs->planes + (size_t)x.lo * (MK_N_PAIR_BASE + pspec->n_thresholds) * np * n_test;
+      return mk_session_pairs(x.ses, &m);
+    });
+    if (rc) return rc;
+    const bool median = comb && comb->method == MK_COMBINE_MEDIAN;
+    const int it = comb && comb->max_iter > 0 ? comb->max_iter : 100;
+    const double tol = comb && comb->tol >= 0.0 ? comb->tol : 1e-12;
+    const std::pair<const double*, double*> todo[2] = {{h_both, pairs->combined_both}, {h_diff, pairs->combined_diff}};
+    for (const auto& g : todo)
+      if (g.second && (rc = median ? mk_combine_median(g.first, K, L, (int64_t)np * n_test, it, tol, g.second, nullptr, devices[0])
+                                   : mk_combine(g.first, K, (int64_t)Gp, g.second, devices[0])))
+        return rc;
+  }
   if (diag) {   // the worst rows over all K: the blocks' own, folded here
     bool first = true;
     for (int r = 0; r < G; ++r) {

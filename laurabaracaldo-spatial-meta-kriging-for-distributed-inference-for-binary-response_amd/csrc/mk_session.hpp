@@ -10,6 +10,7 @@
 //   mk_criteria.hip  model assessment (DIC, WAIC): the kernels, the scratch, the session entry points
 //   mk_scores.hip    held-out validation (log score, Brier, error rate): the kernels, the entry points
 //   mk_maps.hip      posterior maps (mean, sd, exceedance of p(y = 1)): the kernel, the entry points
+//   mk_pairs.hip     cross-outcome prediction (co-occurrence and contrast of two outcomes): the kernels, the entry points
 //
 // mk_internal.hpp stays the interface towards mk_multi.hip and mk_watch.hip.
 #pragma once
@@ -50,7 +51,7 @@ static inline int env_int(const char* name, int dflt) {
   return (v && *v) ? std::atoi(v) : dflt;
 }
 
-constexpr int NKSTAT = 18;
+constexpr int NKSTAT = 19;
 // KS_CHOL_UPDATE: the 128-tile panel-update launches (k_chol_update<128>); KS_CHOL_UPDATE_SUB:
 // the 64- / 32-sub-tile ones (small grids).  Together: the roofline kernel k_chol_update.
 // KS_UPDATE_BUSY: both, with the time of launches that overlap (the split schedule's bulk and
@@ -60,7 +61,7 @@ constexpr int NKSTAT = 18;
 // KS_COV: the candidates' covariance assembly (k_cov_candidate, with k_matern_table for Matern).
 enum { KS_CHOL_UPDATE = 0, KS_CHOL_DIAG, KS_CHOL_TRSM, KS_SWEEP, KS_LAUUM, KS_ITER, KS_INV, KS_CHOL_UPDATE_SUB,
        KS_UPDATE_BUSY, KS_PRED_VAR, KS_COV, KS_SWEEP_FALLBACK, KS_KRIG_CHEB, KS_KRIG_FALLBACK, KS_DIAG, KS_CRIT,
-       KS_SCORE, KS_MAPS };
+       KS_SCORE, KS_MAPS, KS_PAIRS };
 // KS_KRIG_CHEB: tiles kriged by phi interpolation (predict_tile_cheb): launches = tiles, flops = exact
 // s evaluations (one per (subset, outcome) pair and node or check point), total_ms = the largest check
 // difference seen over all pairs and sites (not a time).  KS_KRIG_FALLBACK: tiles whose check failed
@@ -76,6 +77,9 @@ enum { KS_CHOL_UPDATE = 0, KS_CHOL_DIAG, KS_CHOL_TRSM, KS_SWEEP, KS_LAUUM, KS_IT
 // KS_MAPS: the posterior-map launches (k_map_cols per tile replay of a tiled session, per mk_session_maps of
 // a fused one), bracketed by events whether or not the profiler is on; none are made unless maps were asked
 // for.
+// KS_PAIRS: the cross-outcome launches (k_quantiles_pair and k_pair_cols per tile replay of a tiled session,
+// what mk_session_pairs is asked for of a fused one; launches counts kernels), bracketed by events whether or
+// not the profiler is on; none are made unless pairs were asked for.
 // KS_SWEEP_FALLBACK: launches = (subset, iteration) sweeps k_sweep_mg refused admission and its
 // k_sweep fallback ran (counted on the device, read at the end of every mk_session_run; no timing).
 
@@ -256,6 +260,17 @@ struct Maps {
   int lo = -1, n = -1;        // the kept window those replays ran over
 };
 
+// mk_pairs.hip.  Cross-outcome prediction (mk_session_set_pairs): the thresholds and, for a tiled session,
+// the grids and planes its tile replays fill (allocated when pairs are asked for, never otherwise).
+struct Pairs {
+  bool on = false;
+  MapThr th{};
+  double* grids = nullptr;    // tiled: [S][2][C2][200], both then diff; C2 = n_pairs n_test_all
+  double* planes = nullptr;   // tiled: [S][MK_N_PAIR_BASE + J][C2]
+  std::vector<char> done;     // tiled: per tile, replayed since the pairs were attached
+  int lo = -1, n = -1;        // the kept window those replays ran over
+};
+
 }  // namespace mk
 
 struct mk_session {
@@ -295,6 +310,7 @@ struct mk_session {
   mk::Criteria crit;
   mk::Validation val;
   mk::Maps maps;
+  mk::Pairs pairs;
   mk_diagnostics diag_sink{};           // mk_session_set_diagnostics: filled by every tile replay while diag_on
   bool diag_on = false;
   hipError_t launch_err = hipSuccess;   // first failed kernel launch of a run
@@ -434,5 +450,12 @@ void maps_detach(mk_session* s);
 // thresholds[0 .. J) into th (the slots past J at +inf); MK_E_ARG naming the index of a non-finite value, or J
 // when it is outside 0 .. MK_MAP_MAXT.  Touches no device.
 int map_thresholds(const double* thresholds, int J, MapThr* th);
+
+// ---- mk_pairs.hip
+// The pairs' share of tile [t0, ..): the grids and planes of the tile's pair columns, from the draws in
+// md.w_pred ([S][n_kept][Ct]), into the session's buffers.  Timed as KS_PAIRS; returns after the stream is idle.
+int tile_pairs(mk_session* s, int t0, int n_kept, int Ct);
+// Frees the pair buffers and forgets the thresholds (mk_session_set_test_sites; a NULL spec).
+void pairs_detach(mk_session* s);
 
 }  // namespace mk

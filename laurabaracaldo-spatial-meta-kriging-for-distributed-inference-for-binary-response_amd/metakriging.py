@@ -90,7 +90,7 @@ def r_sample_replace(n, size, seed):
 
 def meta_fit(y, x, weight, coords, q, index_part, coords_test=None, cfg=None, subset_base=0, device=0,
              cov_model="exponential", n_batch=100, batch_length=50, seed=20250114, x_test=None, diagnostics=False,
-             criteria=False, y_test=None, weights_test=1, maps=None):
+             criteria=False, y_test=None, weights_test=1, maps=None, pairs=None):
     """All subsets of one shard on one GPU; returns the list `obj` of MK.R:108 for those subsets:
     [{'parameters': 200 x P, 'w.predict': 200 x (q n_test)}, ...]; with x_test (MK.R:87's x.test) each
     also holds 'p.predict' (200 x (q n_test)): the grid of p(y = 1) at the test sites.
@@ -101,7 +101,11 @@ def meta_fit(y, x, weight, coords, q, index_part, coords_test=None, cfg=None, su
     y_test (with weights_test trials; needs x_test): each also holds 'scores', the subset's held-out row by
     name (n, lpd, brier, err, lconst; Session.scores) of its posterior predictive at the test sites.
     maps (exceedance thresholds, () for none; needs x_test): each also holds 'maps', the subset's (q n_test) x
-    (4 + J) planes, and 'maps.names' (w_mean, w_sd, p_mean, p_sd, exc_1..J; Session.maps)."""
+    (4 + J) planes, and 'maps.names' (w_mean, w_sd, p_mean, p_sd, exc_1..J; Session.maps).
+    pairs (joint-exceedance thresholds, () for none; needs x_test and q >= 2): each also holds 'both.predict' and
+    'diff.predict' (200 x C2: the grids of p_a p_b and p_a - p_b per site and outcome pair), 'pairs' (C2 x
+    (6 + J) planes), 'pairs.names' (both_mean, both_sd, diff_mean, diff_sd, corr, a_gt_b, joint_1..J) and
+    'pairs.list' (the (a, b) in column order; Session.pairs)."""
     p = np.asarray(x).shape[1]
     if cfg is None:
         beta0, bt = start_values(y, x, weight, q)
@@ -114,11 +118,14 @@ def meta_fit(y, x, weight, coords, q, index_part, coords_test=None, cfg=None, su
             ses.set_validation(y_test, weights_test)
         if maps is not None:
             ses.set_maps(maps)
+        if pairs is not None:
+            ses.set_pairs(pairs)
         ses.run(cfg.n_samples)
         out = ses.outputs(diagnostics=diagnostics)
         crit = ses.criteria() if criteria else None
         scores = ses.scores() if y_test is not None else None
         planes = ses.maps() if maps is not None else None
+        pr = ses.pairs() if pairs is not None else None
     res = []
     for i in range(len(subsets)):
         d = {"parameters": out["parameters"][i]}
@@ -135,6 +142,9 @@ def meta_fit(y, x, weight, coords, q, index_part, coords_test=None, cfg=None, su
             d["scores"] = dict(zip(scores["names"], scores["subsets"][i].tolist()))
         if planes is not None:
             d["maps"], d["maps.names"] = planes["subsets"][i], list(planes["names"])
+        if pr is not None:
+            d["both.predict"], d["diff.predict"] = pr["both_predict"][i], pr["diff_predict"][i]
+            d["pairs"], d["pairs.names"], d["pairs.list"] = pr["subsets"][i], list(pr["names"]), list(pr["pairs"])
         res.append(d)
     return res
 
@@ -269,7 +279,7 @@ def posterior_summary(result, result2, x_test, q=None, samplesize=1000, seed=202
 
 def reference_flow(d, K, q, cov_model="exponential", n_batch=100, batch_length=50, seed=20250114, devices=(0,),
                    method="mean", predict_tile=0, partition_method="R", samplesize=1000, progress=None,
-                   predictive=False, diagnostics=False, criteria=False, validate=False, maps=None):
+                   predictive=False, diagnostics=False, criteria=False, validate=False, maps=None, pairs=None):
     """The reference script end to end in one process over the GPUs in `devices` (mk_meta_fit: the
     subsets sharded over them in-library, the combine device to device):
 
@@ -294,6 +304,10 @@ def reference_flow(d, K, q, cov_model="exponential", n_batch=100, batch_length=5
     maps (exceedance thresholds, () for none; implies predictive): summary["maps"] holds 'names', 'thresholds'
     and 'combined' ((q n_test) x (4 + J): the combined grids' mean, sd and exceedance planes, meta_fit_node's
     'maps_combined') and 'subsets' (per subset the same planes of its own posterior).
+    pairs (joint-exceedance thresholds, () for none; implies predictive; q >= 2): summary["pairs"] holds
+    meta_fit_node's 'pairs' dict (names, pairs, thresholds and per subset the grids and planes) plus
+    'result_both' / 'result_diff' (200 x C2: the combined grids of p_a p_b and p_a - p_b) and 'combined'
+    (meta_fit_node's 'pairs_combined': map_grid's planes of the two combined grids).
     Returns (phases, result, result2, summary, cfg) -- phases in seconds of
     wall clock: set-up (partition, glm, subset slicing), the chains (to the last batch boundary),
     quantiles + combine, post-processing, and the whole."""
@@ -318,10 +332,10 @@ def reference_flow(d, K, q, cov_model="exponential", n_batch=100, batch_length=5
         return bool(progress(it, n_samples)) if progress is not None else False
 
     fit = meta_fit_node(subs, cfg, coords_test=d["coords_test"], devices=devices, method=method, per_subset=False,
-                        progress=_progress, x_test=d["x_test"] if predictive or validate or maps is not None else None,
+                        progress=_progress, x_test=d["x_test"] if predictive or validate or maps is not None or pairs is not None else None,
                         diagnostics=diagnostics, criteria=criteria,
                         validation=dict(y_test=d["y_test"], pointwise=True) if validate else None,
-                        maps=maps)                                                           # MK.R:100-133
+                        maps=maps, pairs=pairs)                                              # MK.R:100-133
     t3 = time.perf_counter()
     t["chains_s"] = stamp.get("chains", t3) - t1
     t["quantiles_combine_s"] = t3 - stamp.get("chains", t3)
@@ -337,6 +351,9 @@ def reference_flow(d, K, q, cov_model="exponential", n_batch=100, batch_length=5
         summ["criteria"] = dict(zip(fit["criteria"]["names"], fit["criteria"]["total"].tolist()))
     if maps is not None:
         summ["maps"] = dict(fit["maps"], combined=fit["maps_combined"])
+    if pairs is not None:
+        summ["pairs"] = dict(fit["pairs"], result_both=fit["result_both"], result_diff=fit["result_diff"],
+                             combined=fit["pairs_combined"])
     if validate:
         sc = fit["scores"]
         summ["validation"] = dict(combined=sc["combined"], subsets=sc["subsets"], names=sc["names"],

@@ -15,9 +15,9 @@ import numpy as np
 
 from . import _lib
 from ._lib import Combined, check
-from .outbuf import (CriteriaBuffers, DiagnosticBuffers, MapBuffers, OutputBuffers, ScoreBuffers, map_spec,
-                     validation_arrays)
-from .session import PackedProblem
+from .outbuf import (CriteriaBuffers, DiagnosticBuffers, MapBuffers, OutputBuffers, PairBuffers, ScoreBuffers, map_spec,
+                     pair_spec, validation_arrays)
+from .session import PackedProblem, map_grid
 
 N_LEVELS = _lib.N_LEVELS
 
@@ -25,7 +25,7 @@ N_LEVELS = _lib.N_LEVELS
 def meta_fit_node(subsets, cfg, coords_test=None, devices=(0,), subset_base=0, method="mean", per_subset=True,
                   samples=False, w_samples=False, w_pred_samples=False, acceptance=False, w_predict_sum=False,
                   progress=None, record_w=False, max_iter=100, tol=1e-12, x_test=None, p_pred_samples=False,
-                  p_predict_sum=False, diagnostics=False, criteria=False, validation=None, maps=None):
+                  p_predict_sum=False, diagnostics=False, criteria=False, validation=None, maps=None, pairs=None):
     """Fit all subsets over `devices` and combine.  Returns a dict with 'result' (200 x P, MK.R:127),
     'result2' (200 x q n_test, MK.R:133; None without test sites), 'exchange' ('rccl' / 'copy'),
     'comm_ranks' (the ranks the exchange spans: RCCL's own ncclCommCount, or the blocks for copies),
@@ -48,7 +48,12 @@ def meta_fit_node(subsets, cfg, coords_test=None, devices=(0,), subset_base=0, m
     maps (mk_meta_fit_maps): exceedance thresholds on the probability scale (() for none; None: no maps)
     -- adds 'maps': Session.maps' dict for all K subsets ('names': w_mean, w_sd, p_mean, p_sd, exc_1..J;
     'thresholds'; 'subsets': per subset C x (4 + J)) and 'maps_combined' (C x (4 + J)): the same planes of
-    the combined grids, w_mean and w_sd from result2, the others from result3 (map_grid's).  Needs x_test."""
+    the combined grids, w_mean and w_sd from result2, the others from result3 (map_grid's).  Needs x_test.
+    pairs (mk_meta_fit_pairs; q >= 2): joint-exceedance thresholds (() for none; None: no pair outputs) -- adds
+    'pairs': Session.pairs' dict for all K subsets, 'result_both' / 'result_diff' (200 x C2: the K subsets'
+    grids of p_a p_b and p_a - p_b combined by `method`, on the host copies of all K grids: K 200 C2 8 bytes
+    per functional) and 'pairs_combined': {'both': map_grid of result_both with the thresholds, 'diff':
+    map_grid of result_diff with the threshold 0 -- its exc_1 is the combined P(p_a > p_b)}.  Needs x_test."""
     lib = _lib.load()
     if method not in ("mean", "median"):
         raise ValueError(f"error: unknown combine method '{method}'")
@@ -105,13 +110,21 @@ def meta_fit_node(subsets, cfg, coords_test=None, devices=(0,), subset_base=0, m
             raise ValueError("error: maps need test sites and x_test")
         spec = map_spec(maps)
         mb = MapBuffers(K, C, spec[0].size, combined=True)
-    check(lib.mk_meta_fit_maps(ctypes.byref(pp.c), ctypes.byref(c), devs.ctypes.data_as(_lib._ip), len(devs), fn, None,
-                               ctypes.byref(ob.c), ctypes.byref(cb), ctypes.byref(db.c) if db is not None else None,
-                               ctypes.byref(kb.c) if kb is not None else None,
-                               ctypes.byref(val[2]) if val is not None else None,
-                               ctypes.byref(sb.c) if sb is not None else None,
-                               ctypes.byref(spec[1]) if spec is not None else None,
-                               ctypes.byref(mb.c) if mb is not None else None))
+    pb = pspec = None
+    if pairs is not None:
+        if not have_x:
+            raise ValueError("error: pairs need test sites and x_test")
+        pspec = pair_spec(pairs)
+        pb = PairBuffers(K, q, n_test, pspec[0].size, combined=True)
+    check(lib.mk_meta_fit_pairs(ctypes.byref(pp.c), ctypes.byref(c), devs.ctypes.data_as(_lib._ip), len(devs), fn, None,
+                                ctypes.byref(ob.c), ctypes.byref(cb), ctypes.byref(db.c) if db is not None else None,
+                                ctypes.byref(kb.c) if kb is not None else None,
+                                ctypes.byref(val[2]) if val is not None else None,
+                                ctypes.byref(sb.c) if sb is not None else None,
+                                ctypes.byref(spec[1]) if spec is not None else None,
+                                ctypes.byref(mb.c) if mb is not None else None,
+                                ctypes.byref(pspec[1]) if pspec is not None else None,
+                                ctypes.byref(pb.c) if pb is not None else None))
     del keep
     out = {"result": result.T.copy(), "result2": None if result2 is None else result2.T.copy(),
            "exchange": "rccl" if cb.exchange else "copy", "comm_ranks": int(cb.comm_ranks)}
@@ -127,4 +140,10 @@ def meta_fit_node(subsets, cfg, coords_test=None, devices=(0,), subset_base=0, m
     if mb is not None:
         out["maps"] = mb.unpack(spec[0])
         out["maps_combined"] = out["maps"].pop("combined")
+    if pb is not None:
+        out["pairs"] = pb.unpack(pspec[0])
+        out["result_both"], out["result_diff"] = out["pairs"].pop("combined_both"), out["pairs"].pop("combined_diff")
+        dev = int(devs[0])
+        out["pairs_combined"] = {"both": map_grid(out["result_both"], pspec[0], device=dev),
+                                 "diff": map_grid(out["result_diff"], (0.0,), device=dev)}
     return out

@@ -2,8 +2,9 @@
 caller's layouts: one table of field -> shape serves Session.outputs and meta_fit_node."""
 import numpy as np
 
-from ._lib import (CRIT_NAMES, MAP_BASE_NAMES, N_CRIT, N_DIAG, N_LEVELS, N_MAP_BASE, N_SCORE, SCORE_NAMES, Criteria,
-                   Diagnostics, MapSpec, Maps, Outputs, Scores, Validation, dptr)
+from ._lib import (CRIT_NAMES, MAP_BASE_NAMES, N_CRIT, N_DIAG, N_LEVELS, N_MAP_BASE, N_PAIR_BASE, N_SCORE,
+                   PAIR_BASE_NAMES, SCORE_NAMES, Criteria, Diagnostics, MapSpec, Maps, Outputs, PairSpec, Pairs, Scores,
+                   Validation, dptr)
 
 # The array libmk fills for each mk_outputs field, row-major, in terms of: K subsets, P parameters,
 # C = q n_test kriging columns, L levels, n = n_samples, kept states, B amcmc batches, R = P + 1
@@ -187,4 +188,55 @@ class MapBuffers:
             out["subsets"] = [self.subsets[i].T.copy() for i in range(self.K)]
         if self.combined is not None:
             out["combined"] = self.combined.T.copy()
+        return out
+
+
+def pair_list(q):
+    """The outcome pairs (a, b), a < b, in include/mk.h's order: for a in 0..q-2: for b in a+1..q-1."""
+    return [(a, b) for a in range(int(q) - 1) for b in range(a + 1, int(q))]
+
+
+def pair_spec(thresholds):
+    """Joint-exceedance thresholds as libmk reads them: (the array, the mk_pair_spec pointing at it).  libmk
+    checks them as it checks the maps' (finite, at most MK_MAP_MAXT)."""
+    u = np.ascontiguousarray(np.asarray(thresholds, dtype=np.float64).reshape(-1))
+    m = PairSpec()
+    m.n_thresholds, m.thresholds = int(u.size), (dptr(u) if u.size else None)
+    return u, m
+
+
+def pair_names(J):
+    return list(PAIR_BASE_NAMES) + [f"joint_{j + 1}" for j in range(int(J))]
+
+
+class PairBuffers:
+    """The arrays behind an mk_pairs of K subsets of a q-outcome fit at n_test sites (C2 = n_pairs n_test
+    pair columns, site-major) with J thresholds: `.c` points at them; unpack() gives {'names': both_mean,
+    both_sd, diff_mean, diff_sd, corr, a_gt_b, joint_1..J, 'pairs': the (a, b) list, 'thresholds'} and what
+    was asked for of 'both_predict' / 'diff_predict' (per subset 200 x C2), 'subsets' (per subset C2 x
+    (6 + J)) and, with combined, 'combined_both' / 'combined_diff' (200 x C2)."""
+
+    def __init__(self, K, q, n_test, J, grids=True, planes=True, combined=False):
+        self.K, self.q, self.J = int(K), int(q), int(J)
+        self.C2 = len(pair_list(q)) * int(n_test)
+        g = (self.K, self.C2, N_LEVELS)
+        self.both_predict = np.zeros(g) if grids else None
+        self.diff_predict = np.zeros(g) if grids else None
+        self.planes = np.zeros((self.K, N_PAIR_BASE + self.J, self.C2)) if planes else None
+        self.combined_both = np.zeros(g[1:]) if combined else None
+        self.combined_diff = np.zeros(g[1:]) if combined else None
+        self.c = Pairs()
+        for f in ("both_predict", "diff_predict", "planes", "combined_both", "combined_diff"):
+            setattr(self.c, f, dptr(getattr(self, f)))
+
+    def unpack(self, thresholds=()):
+        out = {"names": pair_names(self.J), "pairs": pair_list(self.q), "thresholds": [float(u) for u in thresholds]}
+        for f in ("both_predict", "diff_predict"):
+            if getattr(self, f) is not None:
+                out[f] = [getattr(self, f)[i].T.copy() for i in range(self.K)]
+        if self.planes is not None:
+            out["subsets"] = [self.planes[i].T.copy() for i in range(self.K)]
+        for f in ("combined_both", "combined_diff"):
+            if getattr(self, f) is not None:
+                out[f] = getattr(self, f).T.copy()
         return out

@@ -10,8 +10,8 @@ import numpy as np
 
 from . import _lib
 from ._lib import Config, Problem, check, dptr, iptr
-from .outbuf import (CriteriaBuffers, DiagnosticBuffers, MapBuffers, OutputBuffers, ScoreBuffers, map_names, map_spec,
-                     validation_arrays)
+from .outbuf import (CriteriaBuffers, DiagnosticBuffers, MapBuffers, OutputBuffers, PairBuffers, ScoreBuffers, map_names,
+                     map_spec, pair_spec, validation_arrays)
 
 COV_MODELS = {"exponential": _lib.MK_COV_EXPONENTIAL, "matern": _lib.MK_COV_MATERN}
 LINKS = {"logit": _lib.MK_LINK_LOGIT, "probit": _lib.MK_LINK_PROBIT}
@@ -23,6 +23,7 @@ KS_DIAG = 14      # the chain-diagnostic launches (always timed; 0 launches unle
 KS_CRIT = 15      # the model-assessment launches (always timed; 0 launches unless criteria were asked for)
 KS_SCORE = 16     # the held-out scoring launches (always timed; 0 launches unless validation data were attached)
 KS_MAPS = 17      # the posterior-map launches (always timed; 0 launches unless maps were asked for)
+KS_PAIRS = 18     # the cross-outcome launches (always timed; 0 launches unless pairs were asked for)
 
 
 def _f64(a):
@@ -189,6 +190,7 @@ class Session:
         self._lib = lib
         self._window = None     # kept states of the next outputs(), once set_kept_window narrowed them
         self._map_thresholds = None     # set_maps' thresholds while maps are attached
+        self._pair_thresholds = None    # set_pairs' thresholds while pairs are attached
         # kriging fused into the kept iterations (mk_session_create's rule): a kept window then serves
         # criteria() alone, outputs() keeps every kept state
         self._fused = not (cfg.predict_tile > 0 and (self.n_test == 0 or cfg.predict_tile < self.n_test))
@@ -236,6 +238,7 @@ class Session:
         self.coords_test = _f64(ct.ravel(order="F"))
         self.x_test = None
         self._map_thresholds = None     # the library detaches the maps with the sites
+        self._pair_thresholds = None    # and the pairs
         check(self._lib.mk_session_set_test_sites(self._h, self.n_test, dptr(self.coords_test)))
         if xt is not None:
             self.set_test_covars(xt, _flat=True)
@@ -355,6 +358,34 @@ class Session:
         mb = MapBuffers(self.S, self.q * self.n_test, u.size)
         check(self._lib.mk_session_maps(self._h, ctypes.byref(mb.c)))
         return mb.unpack(u)
+
+    def set_pairs(self, thresholds=()):
+        """Ask for the cross-outcome outputs at the current test sites (mk_session_set_pairs; q >= 2): per
+        site and pair of outcomes (a, b) the 200-level grids of p_a p_b (both occur) and p_a - p_b, and the
+        planes both_mean, both_sd, diff_mean, diff_sd, corr, a_gt_b and, per threshold u (at most 8), the
+        posterior probability that p_a > u and p_b > u.  Needs test sites and x_test.  pairs() then gives
+        them; a tiled session fills each tile's pair columns from the replay that makes its grids
+        (outputs(), tile_grids()).  thresholds=None detaches; so does set_test_sites."""
+        self._pair_thresholds = None
+        if thresholds is None:
+            check(self._lib.mk_session_set_pairs(self._h, None))
+            return
+        u, m = pair_spec(thresholds)
+        check(self._lib.mk_session_set_pairs(self._h, ctypes.byref(m)))
+        self._pair_thresholds = u
+
+    def pairs(self, grids=True, planes=True):
+        """The cross-outcome outputs per subset after the run (mk_session_pairs; the definitions are in
+        include/mk.h): {'names': both_mean, both_sd, diff_mean, diff_sd, corr, a_gt_b, joint_1..J, 'pairs': the
+        (a, b) list in column order, 'thresholds', 'both_predict' / 'diff_predict': per subset 200 x C2,
+        'subsets': per subset C2 x (6 + J)}, C2 = n_pairs n_test pair columns, site-major.  grids=False /
+        planes=False leave that part out (a fused session then does not compute it).  A tiled session must
+        have replayed every tile over the current kept window since set_pairs (MkError naming the first
+        missing tile otherwise)."""
+        u = self._pair_thresholds if self._pair_thresholds is not None else np.zeros(0)
+        pb = PairBuffers(self.S, self.q, self.n_test, u.size, grids=grids, planes=planes)
+        check(self._lib.mk_session_pairs(self._h, ctypes.byref(pb.c)))
+        return pb.unpack(u)
 
     def set_lookahead(self, mode):
         """Launch schedule before the first run: True / 1 lookahead (the next iteration's phi

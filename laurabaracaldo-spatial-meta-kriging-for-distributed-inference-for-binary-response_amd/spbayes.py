@@ -233,6 +233,44 @@ def spMaps(sp_obj, pred_coords, pred_covars, thresholds=(), start=1, end=None):
     return res
 
 
+def spPairs(sp_obj, pred_coords, pred_covars, thresholds=(), start=1, end=None):
+    """Cross-outcome prediction of a multivariate (q >= 2) spMvGLM fit at pred_coords, on the device: per
+    site and pair of outcomes (a, b), a < b -- columns site-major, the pairs in the order "pairs" lists -- the
+    200-level grids "both.predict" of p_a p_b = P(y_a = 1, y_b = 1) and "diff.predict" of p_a - p_b (each 200 x
+    C2), "both.mean", "both.sd", "diff.mean", "diff.sd", "corr" (the posterior correlation of p_a and p_b) and
+    "a.gt.b" (P(p_a > p_b)) (each C2), and "joint" (C2 x J): the posterior probability that both p_a and p_b
+    exceed each threshold; over iterations start..end (1-based, inclusive), kriged from the recorded chain
+    in one replay -- the draws never leave the device.  The definitions are in include/mk.h."""
+    ses = sp_obj.get("_session")
+    if ses is None:
+        raise ValueError("error: the spMvGLM fit was closed; spPairs needs its recorded chain states")
+    if ses.q < 2:
+        raise ValueError("error: spPairs needs a fit with q >= 2 outcomes")
+    n_samples = sp_obj["_n_samples"]
+    end = n_samples if end is None else int(end)
+    start = int(start)
+    if not (1 <= start <= end <= n_samples):
+        raise ValueError("error: invalid start/end")
+    ct = np.asarray(pred_coords, float).reshape(-1, 2)
+    xt = np.asarray(pred_covars, float)
+    if xt.ndim != 2 or xt.shape[0] != ses.q * ct.shape[0]:
+        raise ValueError("error: pred.covars must have one row per prediction site and outcome (q * n rows)")
+    ses.set_test_sites(ct, x_test=pred_covars)
+    ses.set_kept_window(start, end)
+    ses.set_pairs(thresholds)
+    try:
+        ses.outputs(quantiles=False, w_predict_sum=True)      # the one replay of the window
+        m = ses.pairs()
+    finally:
+        ses.set_pairs(None)
+    pl = m["subsets"][0]
+    res = {"both.predict": m["both_predict"][0], "diff.predict": m["diff_predict"][0]}
+    res.update({k.replace("_", "."): pl[:, i].copy() for i, k in enumerate(m["names"][:6])})
+    res["joint"] = pl[:, 6:].copy()
+    res["pairs"], res["thresholds"] = m["pairs"], m["thresholds"]
+    return res
+
+
 def spPredict(sp_obj, pred_coords, pred_covars=None, start=1, end=None, thin=1, diagnostics=False):
     """p.w.predictive.samples ((q n_test) x kept) for kept iterations start..end (1-based,
     inclusive; every thin-th), kriged from the chain states spMvGLM recorded (no refit).

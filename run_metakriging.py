@@ -79,14 +79,25 @@ def main():
                          ".npy (--maps-out); one more JSON line, {\"maps\": the file, the planes' names, per "
                          "threshold the share of sites whose exceedance probability is >= 0.95}")
     ap.add_argument("--maps-out", default="maps_combined.npy", help="where --maps saves the combined planes")
+    ap.add_argument("--pairs", default=None, metavar="U1,U2,...",
+                    help="cross-outcome prediction of a multivariate config (q >= 2: --config 4), e.g. 0.2,0.5 (at most "
+                         "8 thresholds; '' for none): per test site and outcome pair (a, b) the combined 200-level "
+                         "grids of p_a p_b (both occur) and p_a - p_b, saved as 200 x C2 .npy, and their planes "
+                         "(mean, sd, exceedances; of the difference P(diff > 0)) saved as .npy (--pairs-out is the "
+                         "prefix); one more JSON line, {\"pairs\": the files, per pair the share of sites with "
+                         "combined P(p_a > p_b) >= 0.95}; one process (plain or --devices)")
+    ap.add_argument("--pairs-out", default="pairs", help="prefix of the files --pairs saves")
     a = ap.parse_args()
     a.map_thresholds = None if a.maps is None else [float(u) for u in a.maps.split(",") if u.strip()]
+    a.pair_thresholds = None if a.pairs is None else [float(u) for u in a.pairs.split(",") if u.strip()]
     c = dict(CONFIGS[a.config])
     for k_arg, k_cfg in [("n", "n"), ("subsets", "K"), ("n_test", "n_test"), ("n_batch", "n_batch"),
                          ("batch_length", "batch_length"), ("predict_tile", "predict_tile")]:
         v = getattr(a, k_arg)
         if v is not None:
             c[k_cfg] = v
+    if a.pair_thresholds is not None and c["q"] < 2:
+        ap.error(f"--pairs needs a multivariate config: --config {a.config} has q = {c['q']} (--config 4 is q = 3)")
     if a.devices is not None:
         return node_main(a, c)
     rank = int(os.environ.get("RANK", "0"))
@@ -95,8 +106,11 @@ def main():
         ap.error("--diagnostics runs in one process: plain, or over several GPUs with --devices")
     if a.criteria and world > 1:
         ap.error("--criteria runs in one process: plain, or over several GPUs with --devices")
+    if a.pair_thresholds is not None and world > 1:
+        ap.error("--pairs runs in one process: plain, or over several GPUs with --devices")
     local = int(os.environ.get("LOCAL_RANK", "0"))
-    need_p = a.validate or a.map_thresholds is not None      # the combined grid of p(y = 1), result3
+    # the combined grid of p(y = 1), result3; the pairs need x.test on the device as it does
+    need_p = a.validate or a.map_thresholds is not None or a.pair_thresholds is not None
     dist = None
     if world > 1:
         import torch
@@ -133,6 +147,8 @@ def main():
                          criteria=a.criteria)
         if a.validate and world == 1:             # scored per subset: now (fused) or by the tile replays
             ses.set_validation(d["y_test"])
+        if a.pair_thresholds is not None:         # filled now (fused) or by the tile replays
+            ses.set_pairs(a.pair_thresholds)
         for b in range(cfg.n_batch):          # progress every n.report = 10 batches (MK.R:84)
             ses.run(cfg.batch_length)
             if rank == 0 and (b + 1) % 10 == 0:
@@ -228,6 +244,11 @@ def main():
                   file=sys.stderr, flush=True)
     if a.validate and world == 1 and big:
         scores = ses.scores()                     # every tile has been replayed
+    pair_grids = None
+    if a.pair_thresholds is not None:             # fused: made now; tiled: every tile has been replayed
+        pr = ses.pairs(planes=False)
+        comb = mk.metakriging.combiner(a.combine, local)
+        pair_grids = (pr["pairs"], comb(pr["both_predict"]), comb(pr["diff_predict"]))
     krig = None
     if ses is not None and big:                   # how this shard's tiles were kriged (any q)
         cheb, fb = (ses.kernel_stats(k) for k in (mk.session.KS_KRIG_CHEB, mk.session.KS_KRIG_FALLBACK))
@@ -270,6 +291,10 @@ def main():
             w, p = (mk.map_grid(np.asarray(g), u, device=local) for g, u in ((result2, ()), (result3, a.map_thresholds)))
             names = ["w_" + k for k in w["names"]] + ["p_" + k for k in p["names"][:2]] + p["names"][2:]
             print(json.dumps({"maps": maps_line(np.hstack([w["planes"], p["planes"]]), names, a)}), flush=True)
+        if pair_grids is not None:
+            pl = {"both": mk.map_grid(pair_grids[1], a.pair_thresholds, device=local),
+                  "diff": mk.map_grid(pair_grids[2], (0.0,), device=local)}
+            print(json.dumps({"pairs": pairs_line(pair_grids[0], pair_grids[1], pair_grids[2], pl, a)}), flush=True)
     if dist is not None:
         dist.destroy_process_group()
 
@@ -306,6 +331,21 @@ def maps_line(planes, names, a):
             "share_exc_ge_0.95": [float(np.mean(exc[:, j] >= 0.95)) for j in range(exc.shape[1])]}
 
 
+def pairs_line(pairs, both, diff, planes, a):
+    """Saves the combined pair grids (200 x C2 each) and their planes (map_grid's: C2 x (2 + J) of `both`, C2 x 3
+    of `diff`, whose last column is the combined P(p_a > p_b)) and summarises them: per outcome pair the share
+    of test sites where that probability is >= 0.95."""
+    files = {k: f"{a.pairs_out}_{k}.npy" for k in ("both", "diff", "both_planes", "diff_planes")}
+    np.save(files["both"], both)
+    np.save(files["diff"], diff)
+    np.save(files["both_planes"], planes["both"]["planes"])
+    np.save(files["diff_planes"], planes["diff"]["planes"])
+    gt = planes["diff"]["planes"][:, 2].reshape(-1, len(pairs))      # site-major pair columns
+    return {"files": files, "pairs": [list(ab) for ab in pairs], "thresholds": a.pair_thresholds,
+            "both_names": planes["both"]["names"], "diff_names": planes["diff"]["names"],
+            "share_a_gt_b_ge_0.95": [float(np.mean(gt[:, r] >= 0.95)) for r in range(len(pairs))]}
+
+
 def node_main(a, c):
     """The script in one process over a device list (mk_meta_fit): shards, combine (mean or median,
     per test-site tile at configs[4]) and post-processing without torch or a second process."""
@@ -325,7 +365,8 @@ def node_main(a, c):
         d, K, q, cov_model=c["cov"], n_batch=c["n_batch"], batch_length=c["batch_length"], seed=a.seed,
         devices=devices, method=a.combine, predict_tile=c.get("predict_tile", 0), partition_method=a.partition,
         progress=progress, predictive=True,     # MK.R:87's x.test: the grids of p(y = 1) and result3
-        diagnostics=a.diagnostics, criteria=a.criteria, validate=a.validate, maps=a.map_thresholds)
+        diagnostics=a.diagnostics, criteria=a.criteria, validate=a.validate, maps=a.map_thresholds,
+        pairs=a.pair_thresholds)
     ph["data_s"] = data_s
     rec = dict(config=a.config, workload=c, devices=devices, combine=a.combine, phases=ph,
                subset_iters_per_s=K * cfg.n_samples / ph["chains_s"])
@@ -347,6 +388,10 @@ def node_main(a, c):
                                          "auc": v["report"]["auc"]}}), flush=True)
     if a.map_thresholds is not None:
         print(json.dumps({"maps": maps_line(summ["maps"]["combined"], summ["maps"]["names"], a)}), flush=True)
+    if a.pair_thresholds is not None:
+        pr = summ["pairs"]
+        print(json.dumps({"pairs": pairs_line(pr["pairs"], pr["result_both"], pr["result_diff"], pr["combined"], a)}),
+              flush=True)
 
 
 if __name__ == "__main__":
