@@ -10,7 +10,7 @@ SOURCES = ["mk_linalg.hip", "mk_mcmc.hip", "mk_init.hip", "mk_post.hip", "mk_api
            "mk_krig.hip", "mk_summary.hip", "mk_parity.hip", "mk_diag.hip", "mk_criteria.hip",
            "mk_scores.hip", "mk_maps.hip", "mk_pairs.hip", "mk_multi.hip", "mk_watch.hip", "mk_rsample.cpp"]
 HEADERS = ["mk_common.hpp", "mk_types.hpp", "mk_gemm.hpp", "mk_corr.hpp", "mk_kernels.hpp", "mk_internal.hpp",
-           "mk_session.hpp"]
+           "mk_session.hpp", "mk_tilefill.hpp"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wno-unused-value",
          "-Wno-unused-result"]
 
@@ -40,12 +40,12 @@ def build(force=False, verbose=False, out=None, defines=()):
         procs.append((cmd, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)))
         objs.append(obj)
     for cmd, p in procs:
-        out, _ = p.communicate()
+        log, _ = p.communicate()
         if p.returncode != 0:
-            sys.stderr.write(out.decode(errors="replace"))
+            sys.stderr.write(log.decode(errors="replace"))
             raise RuntimeError("hipcc failed: " + " ".join(cmd))
-        if verbose and out:
-            sys.stderr.write(out.decode(errors="replace"))
+        if verbose and log:
+            sys.stderr.write(log.decode(errors="replace"))
     tmp = lib_path + ".tmp"
     cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", tmp] + objs + ["-ldl"]
     subprocess.check_call(cmd)

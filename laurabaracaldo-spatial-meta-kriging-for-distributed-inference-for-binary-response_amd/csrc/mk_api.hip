@@ -35,6 +35,16 @@ int set_err(int code, const std::string& msg) {
   return code;
 }
 int host_error(int code, const char* msg) { return set_err(code, msg); }   // for host-only sources
+
+int results_ready(const mk_session* s, const SinkWords& w, bool on, const TileFill& fill) {
+  if (s->poisoned) return poisoned_err(s);
+  if (!on) return set_err(MK_E_ARG, w.off);
+  if (s->iter < s->md.n_samples) return set_err(MK_E_ARG, w.need_iters);
+  if (!s->tiled) return 0;
+  // the buffer holds the window the tiles were last replayed over
+  const long t = fill.first_missing(s->win_lo, s->win_n < 0 ? s->md.n_kept : s->win_n);
+  return t < 0 ? 0 : set_err(MK_E_ARG, tile_missing_msg(w.what, w.attached, t, s->pred_tile, s->n_test_all));
+}
 }  // namespace mk
 
 extern "C" const char* mk_last_error(void) { return g_err.c_str(); }
@@ -725,7 +735,7 @@ extern "C" int mk_session_create(const mk_problem* pr, const mk_config* c, mk_se
 
 extern "C" int mk_session_run(mk_session* s, int32_t n_iter) {
   if (!s) return set_err(MK_E_ARG, "null session");
-  if (s->poisoned) return set_err(MK_E_HIP, std::string("session unusable after an earlier failure: ") + s->poisoned);
+  if (s->poisoned) return poisoned_err(s);
   MK_ENTRY_DEVICE(s->device);
   if (n_iter < 0 || s->iter + n_iter > s->md.n_samples) return set_err(MK_E_ARG, "n_iter beyond n.samples");
   if (s->la.on && !s->la.c) {
@@ -839,7 +849,7 @@ extern "C" int32_t mk_session_predict_tile(const mk_session* s) { return (s && s
 extern "C" int mk_session_chain_state(mk_session* s, int32_t subset, double* beta, double* theta, double* w,
                                       double* tune, double* accept) {
   if (!s) return set_err(MK_E_ARG, "null session");
-  if (s->poisoned) return set_err(MK_E_HIP, std::string("session unusable after an earlier failure: ") + s->poisoned);
+  if (s->poisoned) return poisoned_err(s);
   if (subset < 0 || subset >= s->S) return set_err(MK_E_ARG, "subset out of range");
   MK_ENTRY_DEVICE(s->device);
   const Model& md = s->md;
@@ -857,7 +867,7 @@ extern "C" int mk_session_chain_state(mk_session* s, int32_t subset, double* bet
 // pivot that is not > 0 (k_theta_mh counts where it reads the flag).
 extern "C" int mk_session_notpd_counts(mk_session* s, int64_t* out) {
   if (!s || !out) return set_err(MK_E_ARG, "null session/output");
-  if (s->poisoned) return set_err(MK_E_HIP, std::string("session unusable after an earlier failure: ") + s->poisoned);
+  if (s->poisoned) return poisoned_err(s);
   MK_ENTRY_DEVICE(s->device);
   static_assert(sizeof(long long) == sizeof(int64_t), "notpd counts are 64-bit");
   HIPCHK(hipStreamSynchronize(s->stream));
@@ -972,7 +982,7 @@ int session_tile_grids(mk_session* s, int t0, double* d_out, mk_outputs* o, doub
 
 extern "C" int mk_session_grids(mk_session* s, int32_t which, double* out, int32_t device_out) {
   if (!s || !out) return set_err(MK_E_ARG, "null session/output");
-  if (s->poisoned) return set_err(MK_E_HIP, std::string("session unusable after an earlier failure: ") + s->poisoned);
+  if (s->poisoned) return poisoned_err(s);
   if (which < 0 || which > 2) return set_err(MK_E_ARG, "which must be 0 (parameters), 1 (w.predict) or 2 (p.predict)");
   if (which >= 1 && s->tiled) return set_err(MK_E_ARG, "tiled sessions give their kriging grids per tile (mk_session_tile_grids)");
   if (which >= 1 && s->md.n_test < 1) return set_err(MK_E_ARG, "the session has no test sites");
@@ -990,7 +1000,7 @@ extern "C" int mk_session_grids(mk_session* s, int32_t which, double* out, int32
 
 extern "C" int mk_session_tile_grids_wp(mk_session* s, int32_t t0, double* out_w, double* out_p, int32_t device_out) {
   if (!s || (!out_w && !out_p)) return set_err(MK_E_ARG, "null session/output");
-  if (s->poisoned) return set_err(MK_E_HIP, std::string("session unusable after an earlier failure: ") + s->poisoned);
+  if (s->poisoned) return poisoned_err(s);
   if (!s->tiled) return set_err(MK_E_ARG, "tile grids need a session created with predict_tile > 0");
   if (out_p && !s->d_xt) return set_err(MK_E_ARG, "p.predict grids need x_test");
   if (device_out) return session_tile_grids(s, t0, out_w, nullptr, out_p);
@@ -1024,7 +1034,7 @@ static void host_layout(double* dst, size_t dr, size_t dc, const double* src, in
 
 extern "C" int mk_session_outputs(mk_session* s, mk_outputs* o) {
   if (!s || !o) return set_err(MK_E_ARG, "null session/outputs");
-  if (s->poisoned) return set_err(MK_E_HIP, std::string("session unusable after an earlier failure: ") + s->poisoned);
+  if (s->poisoned) return poisoned_err(s);
   MK_ENTRY_DEVICE(s->device);
   Model& md = s->md;
   const int S = s->S, P = s->P, q = s->q;

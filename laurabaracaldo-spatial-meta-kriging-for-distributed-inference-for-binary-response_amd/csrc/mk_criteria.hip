@@ -281,19 +281,9 @@ extern "C" int mk_session_set_criteria(mk_session* s, int32_t enable) {
   return 0;
 }
 
-namespace {
-struct CritTimer {
-  hipEvent_t a = nullptr, b = nullptr;
-  ~CritTimer() {
-    if (a) (void)hipEventDestroy(a);
-    if (b) (void)hipEventDestroy(b);
-  }
-};
-}  // namespace
-
 extern "C" int mk_session_criteria(mk_session* s, int32_t thin, mk_criteria* o) {
   if (!s || !o) return set_err(MK_E_ARG, "null session/criteria");
-  if (s->poisoned) return set_err(MK_E_HIP, std::string("session unusable after an earlier failure: ") + s->poisoned);
+  if (s->poisoned) return poisoned_err(s);
   const Model& md = s->md;
   if (thin < 1) return set_err(MK_E_ARG, "thin must be >= 1");
   if (s->iter < md.n_samples) return set_err(MK_E_ARG, "criteria need all n.samples iterations");
@@ -314,9 +304,6 @@ extern "C" int mk_session_criteria(mk_session* s, int32_t thin, mk_criteria* o) 
   DevBufs scratch;
   Crit c = s->crit.buf;
   int launches = 2;
-  CritTimer t;
-  HIPCHK(hipEventCreate(&t.a));
-  HIPCHK(hipEventCreate(&t.b));
   if (!in_chain) {
     c.nb = (md.Np + 255) / 256;
     c.n_cap = n;
@@ -328,7 +315,9 @@ extern "C" int mk_session_criteria(mk_session* s, int32_t thin, mk_criteria* o) 
   double* d_rows = scratch.get<double>((size_t)(S + 1) * MK_N_CRIT);
   double* d_pw = o->pointwise ? scratch.get<double>((size_t)S * 2 * md.Np) : nullptr;
   if (!d_rows || (o->pointwise && !d_pw)) return set_err(MK_E_NOMEM, "criteria scratch");
-  HIPCHK(hipEventRecord(t.a, st));
+  EventTimer t;
+  int rc = t.start(st);
+  if (rc) return rc;
   if (!in_chain) {
     MK_LAUNCH(k_crit_replay, dim3(c.nb, S), dim3(256), 0, st, md, c, md.kept0 + win_lo, n, (int)thin);
     launches += 1;
@@ -336,7 +325,7 @@ extern "C" int mk_session_criteria(mk_session* s, int32_t thin, mk_criteria* o) 
   MK_LAUNCH(k_crit_finish, dim3(S), dim3(256), 0, st, md, c, n, d_rows, d_pw);
   MK_LAUNCH(k_crit_total, dim3(1), dim3(64), 0, st, (const double*)d_rows, S, d_rows + (size_t)S * MK_N_CRIT);
   HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(t.b, st));
+  if ((rc = t.stop(st))) return rc;
   if (o->subsets) HIPCHK(hipMemcpyAsync(o->subsets, d_rows, (size_t)S * MK_N_CRIT * 8, hipMemcpyDeviceToHost, st));
   if (o->total) HIPCHK(hipMemcpyAsync(o->total, d_rows + (size_t)S * MK_N_CRIT, MK_N_CRIT * 8, hipMemcpyDeviceToHost, st));
   if (o->pointwise) {
@@ -348,10 +337,5 @@ extern "C" int mk_session_criteria(mk_session* s, int32_t thin, mk_criteria* o) 
     }
   }
   HIPCHK(hipStreamSynchronize(st));
-  float ms = 0.f;
-  HIPCHK(hipEventElapsedTime(&ms, t.a, t.b));
-  Stat& k = s->prof.stats[KS_CRIT];
-  k.launches += launches;
-  k.ms += ms;
-  return 0;
+  return t.price(s, KS_CRIT, launches);
 }

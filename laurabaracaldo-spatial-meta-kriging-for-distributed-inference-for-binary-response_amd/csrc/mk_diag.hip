@@ -26,17 +26,6 @@ int mk::launch_chain_diag(unsigned grid, hipStream_t st, const double* data, lon
   return 0;
 }
 
-namespace {
-// Events around one diagnostic launch, destroyed on every return path.
-struct DiagTimer {
-  hipEvent_t a = nullptr, b = nullptr;
-  ~DiagTimer() {
-    if (a) (void)hipEventDestroy(a);
-    if (b) (void)hipEventDestroy(b);
-  }
-};
-}  // namespace
-
 int mk::diag_to_host(mk_session* s, const double* data, long subset_stride, long row_stride, int n_rows, long Ct,
                      const ProbSrc* ps, long col0, long C, double* h_each, double* h_worst) {
   if (!h_each && !h_worst) return 0;
@@ -47,13 +36,11 @@ int mk::diag_to_host(mk_session* s, const double* data, long subset_stride, long
   double* dd = scratch.get<double>((size_t)S * Ct * MK_N_DIAG);
   double* dw = h_worst ? scratch.get<double>((size_t)Ct * MK_N_DIAG) : nullptr;
   if (!dd || (h_worst && !dw)) return set_err(MK_E_NOMEM, "diagnostics scratch");
-  DiagTimer t;
-  HIPCHK(hipEventCreate(&t.a));
-  HIPCHK(hipEventCreate(&t.b));
-  HIPCHK(hipEventRecord(t.a, st));
-  const int rc = launch_chain_diag((unsigned)(S * Ct), st, data, subset_stride, row_stride, n_rows, (int)Ct, dd, ps);
+  EventTimer t;
+  int rc = t.start(st);
+  if (!rc) rc = launch_chain_diag((unsigned)(S * Ct), st, data, subset_stride, row_stride, n_rows, (int)Ct, dd, ps);
+  if (!rc) rc = t.stop(st);
   if (rc) return rc;
-  HIPCHK(hipEventRecord(t.b, st));
   const size_t row = (size_t)Ct * MK_N_DIAG * 8;   // one subset's block
   if (h_each)
     HIPCHK(hipMemcpy2DAsync(h_each + (size_t)col0 * MK_N_DIAG, (size_t)C * MK_N_DIAG * 8, dd, row, row, S,
@@ -64,12 +51,7 @@ int mk::diag_to_host(mk_session* s, const double* data, long subset_stride, long
     HIPCHK(hipMemcpyAsync(h_worst + (size_t)col0 * MK_N_DIAG, dw, row, hipMemcpyDeviceToHost, st));
   }
   HIPCHK(hipStreamSynchronize(st));
-  float ms = 0.f;
-  HIPCHK(hipEventElapsedTime(&ms, t.a, t.b));
-  Stat& k = s->prof.stats[KS_DIAG];
-  k.launches += 1;
-  k.ms += ms;
-  return 0;
+  return t.price(s, KS_DIAG, 1);
 }
 
 int mk::tile_diagnostics(mk_session* s, int t0, int n_kept, int Ct) {
@@ -106,7 +88,7 @@ extern "C" int mk_session_set_diagnostics(mk_session* s, const mk_diagnostics* s
 
 extern "C" int mk_session_diagnostics(mk_session* s, mk_diagnostics* o) {
   if (!s || !o) return set_err(MK_E_ARG, "null session/diagnostics");
-  if (s->poisoned) return set_err(MK_E_HIP, std::string("session unusable after an earlier failure: ") + s->poisoned);
+  if (s->poisoned) return poisoned_err(s);
   const Model& md = s->md;
   const bool want_w = o->w_predict || o->w_predict_worst, want_p = o->p_predict || o->p_predict_worst;
   if (s->iter < md.n_samples) return set_err(MK_E_ARG, "chain diagnostics need all n.samples iterations");

@@ -104,6 +104,29 @@ int mk::kriging_buffers(mk_session* s, int n_test_all, const double* coords_test
   return 0;
 }
 
+// The result sinks of a tiled session, in the order a tile replay fills them.  These two functions are the
+// list: a new sink adds one line to each ("adding a sink").
+//
+// The sinks that are on take their share of tile [t0, ..), whose draws are in md.w_pred ([S][n_kept][Ct]),
+// while the draws exist (no second replay); the first error ends it.
+static int tile_sinks(mk_session* s, int t0, int n_kept, int Ct) {
+  int rc = 0;
+  if (s->diag_on) rc = tile_diagnostics(s, t0, n_kept, Ct);
+  if (!rc && s->val.on) rc = tile_scores(s, t0, n_kept, Ct);
+  if (!rc && s->maps.on) rc = tile_maps(s, t0, n_kept, Ct);
+  if (!rc && s->pairs.on) rc = tile_pairs(s, t0, n_kept, Ct);
+  return rc;
+}
+
+// The test sites go: every sink was sized for them, and the held-out data belonged to them.
+static void detach_sinks(mk_session* s) {
+  s->diag_on = false;
+  s->diag_sink = mk_diagnostics{};
+  validation_detach(s);
+  maps_detach(s);
+  pairs_detach(s);
+}
+
 extern "C" int mk_session_set_test_sites(mk_session* s, int32_t n_test, const double* coords_test) {
   if (!s) return set_err(MK_E_ARG, "null session");
   if (!s->tiled)
@@ -111,11 +134,7 @@ extern "C" int mk_session_set_test_sites(mk_session* s, int32_t n_test, const do
   if (n_test < 1 || !coords_test) return set_err(MK_E_ARG, "n_test must be >= 1 with coordinates");
   MK_ENTRY_DEVICE(s->device);
   HIPCHK(hipStreamSynchronize(s->stream));
-  s->diag_on = false;                      // a diagnostics sink was sized for the sites that go
-  s->diag_sink = mk_diagnostics{};
-  validation_detach(s);                    // held-out data belonged to the sites that go
-  maps_detach(s);                          // and the maps' planes were sized for them
-  pairs_detach(s);                         // so were the pair grids and planes
+  detach_sinks(s);
   int rc = set_test_covars(s, nullptr);   // the covariates belonged to the sites that go
   if (rc) return rc;
   return kriging_buffers(s, n_test, coords_test);
@@ -220,26 +239,8 @@ static int tile_outputs(mk_session* s, int t0, double* dq, double* dqp, mk_outpu
       HIPCHK(hipMemcpy2DAsync(o->w_pred_samples + (size_t)i * n_kept * C + (size_t)t0 * q, (size_t)C * 8,
                               md.w_pred + (size_t)i * n_kept * Ct, (size_t)Ct * 8, (size_t)Ct * 8, n_kept,
                               hipMemcpyDeviceToHost, st));
-  // an attached diagnostics sink: this tile's columns, while its draws exist (no second replay)
-  if (s->diag_on) {
-    const int rc = tile_diagnostics(s, t0, n_kept, Ct);
-    if (rc) return rc;
-  }
-  // attached validation data: this tile's columns of the held-out scores, from the same draws
-  if (s->val.on) {
-    const int rc = tile_scores(s, t0, n_kept, Ct);
-    if (rc) return rc;
-  }
-  // maps asked for: this tile's columns of the planes, from the same draws
-  if (s->maps.on) {
-    const int rc = tile_maps(s, t0, n_kept, Ct);
-    if (rc) return rc;
-  }
-  // pairs asked for: this tile's pair columns of the grids and planes, from the same draws
-  if (s->pairs.on) {
-    const int rc = tile_pairs(s, t0, n_kept, Ct);
-    if (rc) return rc;
-  }
+  const int rc = tile_sinks(s, t0, n_kept, Ct);
+  if (rc) return rc;
   HIPCHK(hipStreamSynchronize(st));
   // The replay factored the kept states again.  Each was an accepted candidate of the fit, so a flag
   // here means the device disagreed with itself: an error (the draws above came from a NaN factor),

@@ -77,39 +77,25 @@ using namespace mk;
 
 // ------------------------------------------------------------------ host side
 namespace {
-struct MapTimer {
-  hipEvent_t a = nullptr, b = nullptr;
-  ~MapTimer() {
-    if (a) (void)hipEventDestroy(a);
-    if (b) (void)hipEventDestroy(b);
-  }
-};
+const SinkWords kWords = {"null session/maps", "no posterior maps asked for (mk_session_set_maps)",
+                          "posterior maps need all n.samples iterations", "posterior maps", "the maps were attached"};
 
 // The session form of k_map_cols on the draws in md.w_pred ([S][n][Ct], test row t0 * q first) into
-// planes ([S][4 + J][C]), between the timer's events.  Not waited for.
-int launch_session_maps(mk_session* s, int t0, int n, long Ct, double* planes, MapTimer& t) {
+// planes ([S][4 + J][C]), timed as KS_MAPS.  Returns after the stream is idle.
+int session_maps(mk_session* s, int t0, int n, long Ct, double* planes) {
   const Model& md = s->md;
   const long C = (long)s->q * s->n_test_all;
   hipStream_t st = s->stream;
   const ProbSrc ps = prob_src(s, t0);
-  HIPCHK(hipEventCreate(&t.a));
-  HIPCHK(hipEventCreate(&t.b));
-  HIPCHK(hipEventRecord(t.a, st));
+  EventTimer t;
+  int rc = t.start(st);
+  if (rc) return rc;
   MK_LAUNCH(k_map_cols<false>, dim3((unsigned)((Ct + 255) / 256), s->S), dim3(256), 0, st, (const double*)md.w_pred,
             (long)n * Ct, Ct, 1L, n, (int)Ct, ps, s->maps.th, (long)t0 * s->q, C, planes);
   HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(t.b, st));
-  return 0;
-}
-
-// The stream is idle: the timer's interval into KS_MAPS.
-int price(mk_session* s, const MapTimer& t) {
-  float ms = 0.f;
-  HIPCHK(hipEventElapsedTime(&ms, t.a, t.b));
-  Stat& k = s->prof.stats[KS_MAPS];
-  k.launches += 1;
-  k.ms += ms;
-  return 0;
+  if ((rc = t.stop(st))) return rc;
+  HIPCHK(hipStreamSynchronize(st));
+  return t.price(s, KS_MAPS, 1);
 }
 }  // namespace
 
@@ -141,17 +127,10 @@ void mk::maps_detach(mk_session* s) {
 int mk::tile_maps(mk_session* s, int t0, int n_kept, int Ct) {
   Maps& m = s->maps;
   if (!s->d_xt) return set_err(MK_E_ARG, "posterior maps need x_test");
-  if (m.lo != s->win_lo || m.n != n_kept) {   // another kept window: the tiles filled so far do not go with it
-    std::fill(m.done.begin(), m.done.end(), 0);
-    m.lo = s->win_lo;
-    m.n = n_kept;
-  }
-  MapTimer t;
-  int rc = launch_session_maps(s, t0, n_kept, Ct, m.planes, t);
+  m.fill.begin(s->win_lo, n_kept);
+  const int rc = session_maps(s, t0, n_kept, Ct, m.planes);
   if (rc) return rc;
-  HIPCHK(hipStreamSynchronize(s->stream));
-  if ((rc = price(s, t))) return rc;
-  m.done[(size_t)(t0 / s->pred_tile)] = 1;
+  m.fill.mark(t0);
   return 0;
 }
 
@@ -176,13 +155,12 @@ extern "C" int mk_session_set_maps(mk_session* s, const mk_map_spec* spec) {
     if (rc) {
       maps_detach(s);
       if (rc == MK_E_NOMEM)
-        return set_err(MK_E_NOMEM, "the posterior-map planes (" + std::to_string(8 * (MK_N_MAP_BASE + th.J)) +
-                                       " bytes per subset and test column: " + std::to_string(n * 8) +
-                                       " B) do not fit in HBM beside the kriging buffers: a smaller predict_tile, a "
-                                       "budget MK_KRIG_MEM_GB, or fewer thresholds leave room");
+        return sink_nomem("the posterior-map planes (" + std::to_string(8 * (MK_N_MAP_BASE + th.J)) +
+                              " bytes per subset and test column: ",
+                          n * 8, "do not", "a budget MK_KRIG_MEM_GB, or fewer thresholds leave room");
       return rc;
     }
-    m.done.assign((size_t)((s->n_test_all + s->pred_tile - 1) / s->pred_tile), 0);
+    m.fill.attach(s->n_test_all, s->pred_tile);
   }
   m.th = th;
   m.on = true;
@@ -190,24 +168,9 @@ extern "C" int mk_session_set_maps(mk_session* s, const mk_map_spec* spec) {
 }
 
 extern "C" int mk_session_maps(mk_session* s, mk_maps* o) {
-  if (!s || !o) return set_err(MK_E_ARG, "null session/maps");
-  if (s->poisoned) return set_err(MK_E_HIP, std::string("session unusable after an earlier failure: ") + s->poisoned);
-  const Model& md = s->md;
+  int rc = results_entry(s, o, &mk_session::maps, kWords);
+  if (rc) return rc;
   Maps& m = s->maps;
-  if (!m.on) return set_err(MK_E_ARG, "no posterior maps asked for (mk_session_set_maps)");
-  if (s->iter < md.n_samples) return set_err(MK_E_ARG, "posterior maps need all n.samples iterations");
-  if (s->tiled) {
-    // the planes in the buffer are those of the window the tiles were last replayed over
-    const bool stale = m.lo != s->win_lo || m.n != (s->win_n < 0 ? md.n_kept : s->win_n);
-    for (size_t t = 0; t < m.done.size(); ++t)
-      if (stale || !m.done[t]) {
-        const long a = (long)t * s->pred_tile, b = std::min<long>(a + s->pred_tile, s->n_test_all) - 1;
-        return set_err(MK_E_ARG, "posterior maps: tile " + std::to_string(t) + " (test sites " + std::to_string(a) + " .. " +
-                                     std::to_string(b) +
-                                     ") has not been replayed over this kept window since the maps were attached "
-                                     "(mk_session_outputs, mk_session_tile_grids)");
-      }
-  }
   MK_ENTRY_DEVICE(s->device);
   const long C = (long)s->q * s->n_test_all;
   const size_t len = (size_t)s->S * (MK_N_MAP_BASE + m.th.J) * C;
@@ -217,11 +180,7 @@ extern "C" int mk_session_maps(mk_session* s, mk_maps* o) {
   if (!s->tiled) {   // the fused draws [S][n_kept][C], every kept state
     d_planes = scratch.get<double>(len);
     if (!d_planes) return set_err(MK_E_NOMEM, "posterior-map scratch");
-    MapTimer t;
-    int rc = launch_session_maps(s, 0, md.n_kept, C, d_planes, t);
-    if (rc) return rc;
-    HIPCHK(hipStreamSynchronize(st));
-    if ((rc = price(s, t))) return rc;
+    if ((rc = session_maps(s, 0, s->md.n_kept, C, d_planes))) return rc;
   }
   // [S][4 + J][C] == per subset (q n_test) x (4 + J) column-major
   if (o->subsets) HIPCHK(hipMemcpyAsync(o->subsets, d_planes, len * 8, hipMemcpyDeviceToHost, st));
@@ -237,24 +196,18 @@ extern "C" int mk_map_grid(const double* grid, int32_t n_rows, int64_t n_cols, c
   MapThr th{};
   int rc = map_thresholds(thresholds, n_thresholds, &th);
   if (rc) return rc;
-  // columns per upload: MK_MAP_CHUNK, else 256 MiB of the grid
-  const long by_bytes = std::max<long>(1, (256L << 20) / (8L * n_rows));
-  const long asked = env_int("MK_MAP_CHUNK", 0);
-  const long chunk = std::min<long>(asked > 0 ? asked : by_bytes, (long)n_cols);
+  const long chunk = col_chunk("MK_MAP_CHUNK", n_rows, (long)n_cols);
   MK_ENTRY_DEVICE(device);
   const size_t len = (size_t)(2 + th.J) * n_cols;
   DevBufs bufs;
   double* d_g = bufs.get<double>((size_t)chunk * n_rows);
   double* d_out = bufs.get<double>(len);
   if (!d_g || !d_out) return set_err(MK_E_NOMEM, "map grid buffers");
-  for (long c0 = 0; c0 < n_cols; c0 += chunk) {
-    const long nc = std::min<long>(chunk, (long)n_cols - c0);
-    // the copy returns after the previous chunk's kernel (both on the null stream)
-    HIPCHK(hipMemcpy(d_g, grid + (size_t)c0 * n_rows, (size_t)nc * n_rows * 8, hipMemcpyHostToDevice));
+  rc = upload_col_chunks(grid, n_rows, (long)n_cols, chunk, d_g, [&](long c0, long nc) {
     MK_LAUNCH(k_map_cols<true>, dim3((unsigned)((nc + 255) / 256), 1), dim3(256), 0, (hipStream_t)0, (const double*)d_g, 0L,
               1L, (long)n_rows, (int)n_rows, (int)nc, ProbSrc{}, th, c0, (long)n_cols, d_out);
-    HIPCHK(hipGetLastError());
-  }
+  });
+  if (rc) return rc;
   HIPCHK(hipMemcpy(out, d_out, len * 8, hipMemcpyDeviceToHost));
   HIPCHK(hipDeviceSynchronize());
   return 0;

@@ -138,21 +138,16 @@ using namespace mk;
 
 // ------------------------------------------------------------------ host side
 namespace {
-struct PairTimer {
-  hipEvent_t a = nullptr, b = nullptr;
-  int kernels = 0;
-  ~PairTimer() {
-    if (a) (void)hipEventDestroy(a);
-    if (b) (void)hipEventDestroy(b);
-  }
-};
+const SinkWords kWords = {"null session/pairs", "no cross-outcome prediction asked for (mk_session_set_pairs)",
+                          "cross-outcome prediction needs all n.samples iterations", "cross-outcome prediction",
+                          "the pairs were attached"};
 
 long n_pairs_of(const mk_session* s) { return (long)s->q * (s->q - 1) / 2; }
 
 // The pair kernels on the draws in md.w_pred ([S][n][Ct], test site t0 first): k_quantiles_pair into grids
-// ([S][2][C2][200]) and k_pair_cols into planes ([S][6 + J][C2]), either of which may be NULL, between the
-// timer's events.  Not waited for.
-int launch_session_pairs(mk_session* s, int t0, int n, long Ct, double* grids, double* planes, PairTimer& t) {
+// ([S][2][C2][200]) and k_pair_cols into planes ([S][6 + J][C2]), either of which may be NULL, timed as
+// KS_PAIRS (one launch per kernel).  Returns after the stream is idle.
+int session_pairs(mk_session* s, int t0, int n, long Ct, double* grids, double* planes) {
   const Model& md = s->md;
   const long np = n_pairs_of(s), C2 = np * s->n_test_all;
   const long n_pc = Ct / s->q * np, col0 = (long)t0 * np;
@@ -164,35 +159,26 @@ int launch_session_pairs(mk_session* s, int t0, int n, long Ct, double* grids, d
     if (n < 1 || n > MK_QUANT_MAX)
       return set_err(MK_E_ARG, "quantile summaries take 1 .. " + std::to_string(MK_QUANT_MAX) + " kept samples");
   }
-  HIPCHK(hipEventCreate(&t.a));
-  HIPCHK(hipEventCreate(&t.b));
-  HIPCHK(hipEventRecord(t.a, st));
+  EventTimer t;
+  int rc = t.start(st), kernels = 0;
+  if (rc) return rc;
   if (grids) {
     size_t n2 = 1;
     while (n2 < (size_t)n) n2 <<= 1;
     MK_LAUNCH(k_quantiles_pair, dim3((unsigned)(s->S * n_pc)), dim3(256), n2 * 8, st, (const double*)md.w_pred, (long)n * Ct,
               Ct, n, (int)n_pc, s->q, (const double*)s->d_probs, MK_N_LEVELS, ps, col0, C2, grids);
     HIPCHK(hipGetLastError());
-    ++t.kernels;
+    ++kernels;
   }
   if (planes) {
     MK_LAUNCH(k_pair_cols, dim3((unsigned)((n_pc + 255) / 256), s->S), dim3(256), 0, st, (const double*)md.w_pred,
               (long)n * Ct, Ct, n, (int)n_pc, s->q, ps, s->pairs.th, col0, C2, planes);
     HIPCHK(hipGetLastError());
-    ++t.kernels;
+    ++kernels;
   }
-  HIPCHK(hipEventRecord(t.b, st));
-  return 0;
-}
-
-// The stream is idle: the timer's interval into KS_PAIRS.
-int price(mk_session* s, const PairTimer& t) {
-  float ms = 0.f;
-  HIPCHK(hipEventElapsedTime(&ms, t.a, t.b));
-  Stat& k = s->prof.stats[KS_PAIRS];
-  k.launches += t.kernels;
-  k.ms += ms;
-  return 0;
+  if ((rc = t.stop(st))) return rc;
+  HIPCHK(hipStreamSynchronize(st));
+  return t.price(s, KS_PAIRS, kernels);
 }
 }  // namespace
 
@@ -214,17 +200,10 @@ void mk::pairs_detach(mk_session* s) {
 int mk::tile_pairs(mk_session* s, int t0, int n_kept, int Ct) {
   Pairs& m = s->pairs;
   if (!s->d_xt) return set_err(MK_E_ARG, "cross-outcome prediction needs x_test");
-  if (m.lo != s->win_lo || m.n != n_kept) {   // another kept window: the tiles filled so far do not go with it
-    std::fill(m.done.begin(), m.done.end(), 0);
-    m.lo = s->win_lo;
-    m.n = n_kept;
-  }
-  PairTimer t;
-  int rc = launch_session_pairs(s, t0, n_kept, Ct, m.grids, m.planes, t);
+  m.fill.begin(s->win_lo, n_kept);
+  const int rc = session_pairs(s, t0, n_kept, Ct, m.grids, m.planes);
   if (rc) return rc;
-  HIPCHK(hipStreamSynchronize(s->stream));
-  if ((rc = price(s, t))) return rc;
-  m.done[(size_t)(t0 / s->pred_tile)] = 1;
+  m.fill.mark(t0);
   return 0;
 }
 
@@ -253,13 +232,12 @@ extern "C" int mk_session_set_pairs(mk_session* s, const mk_pair_spec* spec) {
     if (rc) {
       pairs_detach(s);
       if (rc == MK_E_NOMEM)
-        return set_err(MK_E_NOMEM, "the pair grids and planes (" + std::to_string(16 * MK_N_LEVELS + 8 * (MK_N_PAIR_BASE + th.J)) +
-                                       " bytes per subset and pair column: " + std::to_string((ng + npl) * 8) +
-                                       " B) do not fit in HBM beside the kriging buffers: a smaller predict_tile, a "
-                                       "budget MK_KRIG_MEM_GB, or fewer test sites per call leave room");
+        return sink_nomem("the pair grids and planes (" + std::to_string(16 * MK_N_LEVELS + 8 * (MK_N_PAIR_BASE + th.J)) +
+                              " bytes per subset and pair column: ",
+                          (ng + npl) * 8, "do not", "a budget MK_KRIG_MEM_GB, or fewer test sites per call leave room");
       return rc;
     }
-    m.done.assign((size_t)((s->n_test_all + s->pred_tile - 1) / s->pred_tile), 0);
+    m.fill.attach(s->n_test_all, s->pred_tile);
   }
   m.th = th;
   m.on = true;
@@ -267,24 +245,9 @@ extern "C" int mk_session_set_pairs(mk_session* s, const mk_pair_spec* spec) {
 }
 
 extern "C" int mk_session_pairs(mk_session* s, mk_pairs* o) {
-  if (!s || !o) return set_err(MK_E_ARG, "null session/pairs");
-  if (s->poisoned) return set_err(MK_E_HIP, std::string("session unusable after an earlier failure: ") + s->poisoned);
-  const Model& md = s->md;
+  int rc = results_entry(s, o, &mk_session::pairs, kWords);
+  if (rc) return rc;
   Pairs& m = s->pairs;
-  if (!m.on) return set_err(MK_E_ARG, "no cross-outcome prediction asked for (mk_session_set_pairs)");
-  if (s->iter < md.n_samples) return set_err(MK_E_ARG, "cross-outcome prediction needs all n.samples iterations");
-  if (s->tiled) {
-    // the buffers hold the window the tiles were last replayed over
-    const bool stale = m.lo != s->win_lo || m.n != (s->win_n < 0 ? md.n_kept : s->win_n);
-    for (size_t t = 0; t < m.done.size(); ++t)
-      if (stale || !m.done[t]) {
-        const long a = (long)t * s->pred_tile, b = std::min<long>(a + s->pred_tile, s->n_test_all) - 1;
-        return set_err(MK_E_ARG, "cross-outcome prediction: tile " + std::to_string(t) + " (test sites " + std::to_string(a) +
-                                     " .. " + std::to_string(b) +
-                                     ") has not been replayed over this kept window since the pairs were attached "
-                                     "(mk_session_outputs, mk_session_tile_grids)");
-      }
-  }
   MK_ENTRY_DEVICE(s->device);
   const long C2 = n_pairs_of(s) * s->n_test_all;
   const size_t G = (size_t)C2 * MK_N_LEVELS, npl = (size_t)(MK_N_PAIR_BASE + m.th.J) * C2;
@@ -297,13 +260,8 @@ extern "C" int mk_session_pairs(mk_session* s, mk_pairs* o) {
     d_grids = want_g ? scratch.get<double>((size_t)s->S * 2 * G) : nullptr;
     d_planes = o->planes ? scratch.get<double>((size_t)s->S * npl) : nullptr;
     if ((want_g && !d_grids) || (o->planes && !d_planes)) return set_err(MK_E_NOMEM, "cross-outcome scratch");
-    if (d_grids || d_planes) {
-      PairTimer t;
-      int rc = launch_session_pairs(s, 0, md.n_kept, (long)s->q * s->n_test_all, d_grids, d_planes, t);
-      if (rc) return rc;
-      HIPCHK(hipStreamSynchronize(st));
-      if ((rc = price(s, t))) return rc;
-    }
+    if ((d_grids || d_planes) && (rc = session_pairs(s, 0, s->md.n_kept, (long)s->q * s->n_test_all, d_grids, d_planes)))
+      return rc;
   }
   // [S][2][C2][200]: per subset and functional 200 x C2 column-major
   double* const h[2] = {o->both_predict, o->diff_predict};

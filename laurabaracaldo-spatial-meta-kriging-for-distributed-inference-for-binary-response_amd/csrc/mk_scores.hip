@@ -130,13 +130,9 @@ using namespace mk;
 
 // ------------------------------------------------------------------ host side
 namespace {
-struct ScoreTimer {
-  hipEvent_t a = nullptr, b = nullptr;
-  ~ScoreTimer() {
-    if (a) (void)hipEventDestroy(a);
-    if (b) (void)hipEventDestroy(b);
-  }
-};
+const SinkWords kWords = {"null session/scores", "no validation data attached (mk_session_set_validation)",
+                          "held-out scores need all n.samples iterations", "held-out scores",
+                          "the validation data were attached"};
 
 // First index whose (y, wt) is not a count of successes in a count of trials, or -1.
 long first_bad(const double* y, const double* wt, long C) {
@@ -151,17 +147,15 @@ int bad_entry(const double* y, const double* wt, long c) {
 }
 
 // The session form of k_score_cols on the draws in md.w_pred ([S][n][Ct], test row t0 * q first) into
-// pw ([S][2][C]), between the timer's events when t is given.  Not waited for.
-int launch_session_cols(mk_session* s, int t0, int n, long Ct, double* pw, ScoreTimer* t) {
+// pw ([S][2][C]).  Not waited for.
+int launch_session_cols(mk_session* s, int t0, int n, long Ct, double* pw) {
   const Model& md = s->md;
   const long C = (long)s->q * s->n_test_all;
   hipStream_t st = s->stream;
   const ProbSrc ps = prob_src(s, t0);
-  if (t) HIPCHK(hipEventRecord(t->a, st));
   MK_LAUNCH(k_score_cols<false>, dim3((unsigned)((Ct + 255) / 256), s->S), dim3(256), 0, st, (const double*)md.w_pred,
             (long)n * Ct, Ct, 1L, n, (int)Ct, ps, (const double*)s->val.y, (const double*)s->val.wt, (long)t0 * s->q, C, pw);
   HIPCHK(hipGetLastError());
-  if (t) HIPCHK(hipEventRecord(t->b, st));
   return 0;
 }
 }  // namespace
@@ -177,23 +171,15 @@ void mk::validation_detach(mk_session* s) {
 int mk::tile_scores(mk_session* s, int t0, int n_kept, int Ct) {
   Validation& v = s->val;
   if (!s->d_xt) return set_err(MK_E_ARG, "held-out scores need x_test");
-  if (v.lo != s->win_lo || v.n != n_kept) {   // another kept window: the tiles scored so far do not go with it
-    std::fill(v.done.begin(), v.done.end(), 0);
-    v.lo = s->win_lo;
-    v.n = n_kept;
-  }
-  ScoreTimer t;
-  HIPCHK(hipEventCreate(&t.a));
-  HIPCHK(hipEventCreate(&t.b));
-  const int rc = launch_session_cols(s, t0, n_kept, Ct, v.pw, &t);
+  v.fill.begin(s->win_lo, n_kept);
+  EventTimer t;
+  int rc = t.start(s->stream);
+  if (!rc) rc = launch_session_cols(s, t0, n_kept, Ct, v.pw);
+  if (!rc) rc = t.stop(s->stream);
   if (rc) return rc;
   HIPCHK(hipStreamSynchronize(s->stream));
-  float ms = 0.f;
-  HIPCHK(hipEventElapsedTime(&ms, t.a, t.b));
-  Stat& k = s->prof.stats[KS_SCORE];
-  k.launches += 1;
-  k.ms += ms;
-  v.done[(size_t)(t0 / s->pred_tile)] = 1;
+  if ((rc = t.price(s, KS_SCORE, 1))) return rc;
+  v.fill.mark(t0);
   return 0;
 }
 
@@ -217,38 +203,22 @@ extern "C" int mk_session_set_validation(mk_session* s, const mk_validation* val
       (s->tiled && (rc = s->alloc(&v.pw, (size_t)s->S * 2 * C)))) {
     validation_detach(s);
     if (rc == MK_E_NOMEM)
-      return set_err(MK_E_NOMEM, "the held-out score buffer (16 bytes per subset and test column: " +
-                                     std::to_string((size_t)s->S * 2 * C * 8) +
-                                     " B) does not fit in HBM beside the kriging buffers: a smaller predict_tile, or a "
-                                     "budget MK_KRIG_MEM_GB, leaves room");
+      return sink_nomem("the held-out score buffer (16 bytes per subset and test column: ", (size_t)s->S * 2 * C * 8,
+                        "does not", "or a budget MK_KRIG_MEM_GB, leaves room");
     return rc;
   }
   HIPCHK(hipMemcpy(v.y, val->y_test, (size_t)C * 8, hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(v.wt, val->wt_test, (size_t)C * 8, hipMemcpyHostToDevice));
-  if (s->tiled) v.done.assign((size_t)((s->n_test_all + s->pred_tile - 1) / s->pred_tile), 0);
+  if (s->tiled) v.fill.attach(s->n_test_all, s->pred_tile);
   v.on = true;
   return 0;
 }
 
 extern "C" int mk_session_scores(mk_session* s, mk_scores* o) {
-  if (!s || !o) return set_err(MK_E_ARG, "null session/scores");
-  if (s->poisoned) return set_err(MK_E_HIP, std::string("session unusable after an earlier failure: ") + s->poisoned);
+  int rc = results_entry(s, o, &mk_session::val, kWords);
+  if (rc) return rc;
   const Model& md = s->md;
   Validation& v = s->val;
-  if (!v.on) return set_err(MK_E_ARG, "no validation data attached (mk_session_set_validation)");
-  if (s->iter < md.n_samples) return set_err(MK_E_ARG, "held-out scores need all n.samples iterations");
-  if (s->tiled) {
-    // the pairs in the buffer are those of the window the tiles were last replayed over
-    const bool stale = v.lo != s->win_lo || v.n != (s->win_n < 0 ? md.n_kept : s->win_n);
-    for (size_t t = 0; t < v.done.size(); ++t)
-      if (stale || !v.done[t]) {
-        const long a = (long)t * s->pred_tile, b = std::min<long>(a + s->pred_tile, s->n_test_all) - 1;
-        return set_err(MK_E_ARG, "held-out scores: tile " + std::to_string(t) + " (test sites " + std::to_string(a) + " .. " +
-                                     std::to_string(b) +
-                                     ") has not been replayed over this kept window since the validation data were "
-                                     "attached (mk_session_outputs, mk_session_tile_grids)");
-      }
-  }
   MK_ENTRY_DEVICE(s->device);
   const int S = s->S;
   const long C = (long)s->q * s->n_test_all;
@@ -257,29 +227,21 @@ extern "C" int mk_session_scores(mk_session* s, mk_scores* o) {
   double* d_rows = scratch.get<double>((size_t)S * MK_N_SCORE);
   double* d_pw = s->tiled ? v.pw : scratch.get<double>((size_t)S * 2 * C);
   if (!d_rows || !d_pw) return set_err(MK_E_NOMEM, "held-out score scratch");
-  ScoreTimer t;
-  HIPCHK(hipEventCreate(&t.a));
-  HIPCHK(hipEventCreate(&t.b));
-  HIPCHK(hipEventRecord(t.a, st));
+  EventTimer t;
+  if ((rc = t.start(st))) return rc;
   int launches = 1;
   if (!s->tiled) {   // the fused draws [S][n_kept][C], every kept state
-    const int rc = launch_session_cols(s, 0, md.n_kept, C, d_pw, nullptr);
-    if (rc) return rc;
+    if ((rc = launch_session_cols(s, 0, md.n_kept, C, d_pw))) return rc;
     launches += 1;
   }
   MK_LAUNCH(k_score_finish, dim3(S), dim3(256), 0, st, (const double*)d_pw, (const double*)v.y, (const double*)v.wt, C, d_rows);
   HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(t.b, st));
+  if ((rc = t.stop(st))) return rc;
   if (o->subsets) HIPCHK(hipMemcpyAsync(o->subsets, d_rows, (size_t)S * MK_N_SCORE * 8, hipMemcpyDeviceToHost, st));
   // [S][2][C] == per subset (q n_test) x 2 column-major
   if (o->pointwise) HIPCHK(hipMemcpyAsync(o->pointwise, d_pw, (size_t)S * 2 * C * 8, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
-  float ms = 0.f;
-  HIPCHK(hipEventElapsedTime(&ms, t.a, t.b));
-  Stat& k = s->prof.stats[KS_SCORE];
-  k.launches += launches;
-  k.ms += ms;
-  return 0;
+  return t.price(s, KS_SCORE, launches);
 }
 
 extern "C" int mk_score_grid(const double* p, int32_t n_rows, int64_t n_cols, const double* y, const double* wt,
@@ -289,10 +251,7 @@ extern "C" int mk_score_grid(const double* p, int32_t n_rows, int64_t n_cols, co
   if (n_cols < 1 || n_cols > 0x7fffffffL) return set_err(MK_E_ARG, "n_cols must be 1 .. 2^31 - 1");
   const long b = first_bad(y, wt, (long)n_cols);
   if (b >= 0) return bad_entry(y, wt, b);
-  // columns per upload: MK_SCORE_CHUNK, else 256 MiB of p
-  const long by_bytes = std::max<long>(1, (256L << 20) / (8L * n_rows));
-  const long asked = env_int("MK_SCORE_CHUNK", 0);
-  const long chunk = std::min<long>(asked > 0 ? asked : by_bytes, (long)n_cols);
+  const long chunk = col_chunk("MK_SCORE_CHUNK", n_rows, (long)n_cols);
   MK_ENTRY_DEVICE(device);
   DevBufs bufs;
   double* d_p = bufs.get<double>((size_t)chunk * n_rows);
@@ -303,15 +262,12 @@ extern "C" int mk_score_grid(const double* p, int32_t n_rows, int64_t n_cols, co
   if (!d_p || !d_y || !d_wt || !d_pw || !d_row) return set_err(MK_E_NOMEM, "score grid buffers");
   HIPCHK(hipMemcpy(d_y, y, (size_t)n_cols * 8, hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(d_wt, wt, (size_t)n_cols * 8, hipMemcpyHostToDevice));
-  for (long c0 = 0; c0 < n_cols; c0 += chunk) {
-    const long nc = std::min<long>(chunk, (long)n_cols - c0);
-    // the copy returns after the previous chunk's kernel (both on the null stream)
-    HIPCHK(hipMemcpy(d_p, p + (size_t)c0 * n_rows, (size_t)nc * n_rows * 8, hipMemcpyHostToDevice));
+  const int rc = upload_col_chunks(p, n_rows, (long)n_cols, chunk, d_p, [&](long c0, long nc) {
     MK_LAUNCH(k_score_cols<true>, dim3((unsigned)((nc + 255) / 256), 1), dim3(256), 0, (hipStream_t)0, (const double*)d_p, 0L,
               1L, (long)n_rows, (int)n_rows, (int)nc, ProbSrc{}, (const double*)d_y, (const double*)d_wt, c0, (long)n_cols,
               d_pw);
-    HIPCHK(hipGetLastError());
-  }
+  });
+  if (rc) return rc;
   MK_LAUNCH(k_score_finish, dim3(1), dim3(256), 0, (hipStream_t)0, (const double*)d_pw, (const double*)d_y,
             (const double*)d_wt, (long)n_cols, d_row);
   HIPCHK(hipGetLastError());

@@ -12,6 +12,11 @@
 //   mk_maps.hip      posterior maps (mean, sd, exceedance of p(y = 1)): the kernel, the entry points
 //   mk_pairs.hip     cross-outcome prediction (co-occurrence and contrast of two outcomes): the kernels, the entry points
 //
+// What the five result sinks above share is here and in mk_tilefill.hpp: EventTimer (their launches' price),
+// TileFill (which tiles a tiled session's buffer holds, over which kept window), results_entry (the checks a
+// results call starts with), upload_col_chunks (the stand-alone grid entries) and sink_nomem.  The list of
+// sinks a tile replay fills and mk_session_set_test_sites detaches is in mk_krig.hip (tile_sinks, detach_sinks).
+//
 // mk_internal.hpp stays the interface towards mk_multi.hip and mk_watch.hip.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -23,6 +28,7 @@
 #include "../../include/mk.h"
 #include "mk_kernels.hpp"
 #include "mk_internal.hpp"
+#include "mk_tilefill.hpp"
 
 namespace mk {
 int set_err(int code, const std::string& msg);   // mk_api.hip: sets mk_last_error(), returns code
@@ -246,8 +252,7 @@ struct Validation {
   double* y = nullptr;        // [q n_test_all]
   double* wt = nullptr;       // [q n_test_all]
   double* pw = nullptr;       // tiled: [S][2][q n_test_all], plane 0 pmean_c, plane 1 lpd_c
-  std::vector<char> done;     // tiled: per tile, replayed since the data were attached
-  int lo = -1, n = -1;        // the kept window those replays ran over
+  TileFill fill;              // tiled: the tiles scored since the data were attached
 };
 
 // mk_maps.hip.  Posterior maps (mk_session_set_maps): the thresholds and, for a tiled session, the
@@ -256,8 +261,7 @@ struct Maps {
   bool on = false;
   MapThr th{};
   double* planes = nullptr;   // tiled: [S][MK_N_MAP_BASE + J][q n_test_all]
-  std::vector<char> done;     // tiled: per tile, replayed since the maps were attached
-  int lo = -1, n = -1;        // the kept window those replays ran over
+  TileFill fill;              // tiled: the tiles filled since the maps were attached
 };
 
 // mk_pairs.hip.  Cross-outcome prediction (mk_session_set_pairs): the thresholds and, for a tiled session,
@@ -267,8 +271,7 @@ struct Pairs {
   MapThr th{};
   double* grids = nullptr;    // tiled: [S][2][C2][200], both then diff; C2 = n_pairs n_test_all
   double* planes = nullptr;   // tiled: [S][MK_N_PAIR_BASE + J][C2]
-  std::vector<char> done;     // tiled: per tile, replayed since the pairs were attached
-  int lo = -1, n = -1;        // the kept window those replays ran over
+  TileFill fill;              // tiled: the tiles filled since the pairs were attached
 };
 
 }  // namespace mk
@@ -363,6 +366,87 @@ static void timed(mk_session* s, hipStream_t st, int which, double flops, F&& la
   launch();
   hipEventRecord(t.b, st);
   s->prof.pending.push_back(t);
+}
+
+// Events around a sink's launches, bracketed whether or not the profiler is on and destroyed on every
+// return path.  start and stop record on the stream; price, once the stream is idle, adds the interval and
+// the launches it held to the kernel kind's statistics.
+struct EventTimer {
+  hipEvent_t a = nullptr, b = nullptr;
+  EventTimer() = default;
+  EventTimer(const EventTimer&) = delete;
+  ~EventTimer() {
+    if (a) (void)hipEventDestroy(a);
+    if (b) (void)hipEventDestroy(b);
+  }
+  int start(hipStream_t st) {
+    HIPCHK(hipEventCreate(&a));
+    HIPCHK(hipEventCreate(&b));
+    HIPCHK(hipEventRecord(a, st));
+    return 0;
+  }
+  int stop(hipStream_t st) {
+    HIPCHK(hipEventRecord(b, st));
+    return 0;
+  }
+  int price(mk_session* s, int kind, long launches) const {
+    float ms = 0.f;
+    HIPCHK(hipEventElapsedTime(&ms, a, b));
+    Stat& k = s->prof.stats[kind];
+    k.launches += launches;
+    k.ms += ms;
+    return 0;
+  }
+};
+
+// A run left the chain in a state that is not the sampler's: every later call on the session fails with this.
+static inline int poisoned_err(const mk_session* s) {
+  return set_err(MK_E_HIP, std::string("session unusable after an earlier failure: ") + s->poisoned);
+}
+
+// A sink's words in the errors of its results entry (mk_session_scores, _maps, _pairs).
+struct SinkWords {
+  const char* null_args;    // "null session/maps"
+  const char* off;          // "no posterior maps asked for (mk_session_set_maps)"
+  const char* need_iters;   // "posterior maps need all n.samples iterations"
+  const char* what;         // tile_missing_msg's two phrases
+  const char* attached;
+};
+// mk_api.hip.  What a results entry checks before it touches the device: the session usable, the sink on,
+// the chain complete and, for a tiled session, every tile replayed over the current kept window.
+int results_ready(const mk_session* s, const SinkWords& w, bool on, const TileFill& fill);
+template <typename Sink>
+int results_entry(const mk_session* s, const void* o, Sink mk_session::*sink, const SinkWords& w) {
+  if (!s || !o) return set_err(MK_E_ARG, w.null_args);
+  return results_ready(s, w, (s->*sink).on, (s->*sink).fill);
+}
+
+// A tiled session's sink buffer did not fit: what ends "... bytes per subset and test column: ", verb is
+// "does not" or "do not", remedy what follows "a smaller predict_tile, ".
+static inline int sink_nomem(const std::string& what, size_t bytes, const char* verb, const char* remedy) {
+  return set_err(MK_E_NOMEM, what + std::to_string(bytes) + " B) " + verb +
+                                 " fit in HBM beside the kriging buffers: a smaller predict_tile, " + remedy);
+}
+
+// Columns per upload of a stand-alone grid entry (n_rows doubles per column): the environment's count, else
+// 256 MiB of the grid; 1 .. n_cols.
+static inline long col_chunk(const char* env, long n_rows, long n_cols) {
+  const long by_bytes = std::max<long>(1, (256L << 20) / (8L * n_rows));
+  const long asked = env_int(env, 0);
+  return std::min<long>(asked > 0 ? asked : by_bytes, n_cols);
+}
+// The host grid h (n_cols columns of n_rows) through the device buffer d (chunk columns), chunk by chunk:
+// launch(c0, nc) queues the kernel of columns [c0, c0 + nc) on the null stream, where the next chunk's copy
+// returns after it.
+template <typename F>
+int upload_col_chunks(const double* h, long n_rows, long n_cols, long chunk, double* d, F&& launch) {
+  for (long c0 = 0; c0 < n_cols; c0 += chunk) {
+    const long nc = std::min<long>(chunk, n_cols - c0);
+    HIPCHK(hipMemcpy(d, h + (size_t)c0 * n_rows, (size_t)nc * n_rows * 8, hipMemcpyHostToDevice));
+    launch(c0, nc);
+    HIPCHK(hipGetLastError());
+  }
+  return 0;
 }
 
 // ---- mk_api.hip
