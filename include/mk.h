@@ -620,6 +620,18 @@ int mk_r_sample_replace(int32_t seed, int32_t n, int32_t size, int32_t* out);
  * Temme/CF2 Bessel-K evaluation) -- the covariance-assembly arithmetic the chains use. */
 int mk_correlation_batched(const double* coords, int32_t S, int32_t n, const double* phi, const double* nu,
                            int32_t cov_model, double* R_out, int32_t device);
+/* The same, on both routes and both Matern table configurations.  R_out ([S][n][n] column-major, or NULL):
+ * the candidate route, as above.  PT_out ([S][n][n_test], row k the observed site, or NULL): the kriging
+ * route, P^T = correlation(coords_k, coords_test_k) by k_pred_PT_matern (Matern) or k_pred_PT
+ * (exponential); coords_test: [S][2][n_test], every point set with its own test sites (x then y, as
+ * coords: [S][2][n]).  stored_tables (Matern): 1 the configuration of a session -- the Chebyshev tables
+ * cover [0.5, phi x span], span the sites' bounding-box diagonal (R) or the bound on the site-to-test-site
+ * distances (P^T) by the expressions the sessions use, stored by k_matern_table / k_matern_table_list and
+ * loaded by the tile workgroups; 0 the kernels build unbounded tables themselves.
+ * mk_correlation_batched is this call with stored_tables = 0 and R only. */
+int mk_correlation_cross_batched(const double* coords, int32_t S, int32_t n, const double* coords_test,
+                                 int32_t n_test, const double* phi, const double* nu, int32_t cov_model,
+                                 int32_t stored_tables, double* R_out, double* PT_out, int32_t device);
 /* Cholesky (lower) + log-determinant (+ optional inverse) of S SPD n x n matrices.  MK_E_ARG when a
  * factorisation meets a pivot that is not > 0 (negative, zero or NaN); mk_last_error then reads
  * "matrix <i> is not positive definite", i the lowest index of such a matrix. */

@@ -7,7 +7,7 @@ this package is the host-side mirror of the reference's R interface
 """
 from ._lib import MkError, load  # noqa: F401
 from .session import (SamplerConfig, Session, chain_diagnostics, cholesky_batched, combine,  # noqa: F401
-                      correlation_batched, map_grid, score_grid)
+                      correlation_batched, correlation_cross_batched, map_grid, score_grid)
 from .spbayes import spDiag, spDiagnostics, spMaps, spMvGLM, spPairs, spPredict, spValidate  # noqa: F401
 from .glm import glm_binomial  # noqa: F401
 from .post import combine_median  # noqa: F401

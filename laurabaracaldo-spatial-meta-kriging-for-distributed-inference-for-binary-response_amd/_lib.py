@@ -197,6 +197,8 @@ EXPORTS = {
                                        ctypes.c_int32, _dp, _dp, _ip, ctypes.c_int32]),
     "mk_correlation_batched": (ctypes.c_int, [_dp, ctypes.c_int32, ctypes.c_int32, _dp, _dp, ctypes.c_int32, _dp,
                                               ctypes.c_int32]),
+    "mk_correlation_cross_batched": (ctypes.c_int, [_dp, ctypes.c_int32, ctypes.c_int32, _dp, ctypes.c_int32, _dp, _dp,
+                                                    ctypes.c_int32, ctypes.c_int32, _dp, _dp, ctypes.c_int32]),
     "mk_cholesky_batched": (ctypes.c_int, [_dp, ctypes.c_int32, ctypes.c_int32, _dp, _dp, _dp, ctypes.c_int32]),
     "mk_partition_r": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _ip, _ip]),
     "mk_r_sample": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _ip]),

@@ -339,13 +339,7 @@ static void derive_dims(mk_session* s, const mk_problem* pr, const mk_config* c)
     for (int i = 0; i < S; ++i) {
       const int ns = pr->n_part[i];
       const double* cs = pr->coords + 2 * off;
-      double* b = s->bbox.data() + 4 * i;
-      for (int r = 0; r < ns; ++r) {
-        if (r == 0 || cs[r] < b[0]) b[0] = cs[r];
-        if (r == 0 || cs[r] > b[1]) b[1] = cs[r];
-        if (r == 0 || cs[ns + r] < b[2]) b[2] = cs[ns + r];
-        if (r == 0 || cs[ns + r] > b[3]) b[3] = cs[ns + r];
-      }
+      site_bbox(cs, cs + ns, ns, s->bbox.data() + 4 * i);
       off += ns;
     }
   }
@@ -433,8 +427,7 @@ static int alloc_chain_state(mk_session* s, const mk_problem* pr) {
     double* d_span = nullptr;
     if ((rc = s->alloc(&d_span, (size_t)S))) return rc;
     std::vector<double> hs(S);
-    for (int i = 0; i < S; ++i)
-      hs[i] = std::hypot(s->bbox[4 * i + 1] - s->bbox[4 * i], s->bbox[4 * i + 3] - s->bbox[4 * i + 2]);
+    for (int i = 0; i < S; ++i) hs[i] = matern_span(s->bbox.data() + 4 * i);
     HIPCHK(hipMemcpy(d_span, hs.data(), (size_t)S * 8, hipMemcpyHostToDevice));
     md.span = d_span;
     if (s->matern && ((rc = s->alloc(&md.chtab, (size_t)S * q * MK_CH_TAB)) ||

@@ -102,7 +102,11 @@ struct CorrFn {
       const double x2 = 0.5 * x;
       double d = LN2 - lx;
       const double e = mu * d;
-      const double em1 = expm1(e), E = em1 + 1.0, iE = 1.0 / E;
+      // E = expm1(e) + 1 carries an absolute error of an ulp of 1, i.e. a relative one of 2^-53 / E: for
+      // mu < 0 and small x (e << 0) that reached 4e-9 in rho (mu = -0.5, x = 2e-16; 5e-13 at x = 1e-8:
+      // tests/test_gpu_matern.py).  Below e = -1 take exp itself; above, the error stays under 3e-16
+      // (x in [0.5, 2), the range of the Chebyshev tables' series nodes, has e >= -0.7).
+      const double em1 = expm1(e), E = (e < -1.0) ? exp(e) : em1 + 1.0, iE = 1.0 / E;
       const double fact2 = (fabs(e) < EPS) ? 1.0 : 0.5 * em1 * (1.0 + iE) / e;   // sinh(e) / e
       double ff = fact * (gam1 * (0.5 * (E + iE)) + gam2 * fact2 * d);
       double sum = ff;
@@ -187,11 +191,13 @@ struct CorrFn {
     return rkmu;
   }
 
-  // Matern rho at x = phi d: x^nu / (2^(nu-1) Gamma(nu)) K_nu(x), 1 at x = 0
+  // Matern rho at x = phi d: x^nu / (2^(nu-1) Gamma(nu)) K_nu(x), 1 at x = 0.  rho <= 1: as x -> 0
+  // the product rounds to 1 + a few ulps (up to 31 seen), which is cut off (NaN stays NaN).
   __device__ double matern_x(double x) const {
     if (!(x > 0.0)) return 1.0;
     const double lx = log(x);
-    return exp(nu * lx) / den * bessel_k(x, lx);
+    const double v = exp(nu * lx) / den * bessel_k(x, lx);
+    return v > 1.0 ? 1.0 : v;
   }
 
   // rho(d): exponential exp(-phi d); Matern (phi d)^nu / (2^(nu-1) Gamma(nu)) K_nu(phi d), 1 at d = 0
@@ -208,8 +214,12 @@ struct CorrFn {
 // analytic, piecewise Chebyshev series of MK_CH_N terms on intervals [0.5 * 1.25^g, 0.5 * 1.25^(g+1))
 // (g < 7: the singularity of x^(2 nu) at 0 stays >= 9 half-widths away) and then of width 0.5
 // (e^-x varies by e^-0.5 per interval).  Truncation error ~ rho_E^-12 ~ 1e-15 relative for these
-// widths (Bernstein ellipse rho_E >= 17.9); measured against scipy kv: <= 1e-13 relative, nu in [0.05, 4], x in
-// [0.5, 39] (the scipy reference's own accuracy).  x < 0.5 (the non-analytic part) and x beyond
+// widths (Bernstein ellipse rho_E >= 17.9).  Claimed and asserted: <= 1e-13 relative (+ the rounding of x
+// carried to rho, 2 * 2^-52 * x K_|nu-1|(x) / K_nu(x)) against a longdouble quadrature of K_nu, element by
+// element, nu in [0.01, 10], x in [1e-9, 600], tables built here or stored, candidate and kriging
+// kernels (tests/test_gpu_matern.py).  Measured there: <= 4.2e-14, 0.41 of that bar at the worst (nu = 10
+// as x -> 0; 0.13 of it over the tables); scipy's kv, the earlier yardstick, is itself up to 1.0e-13 off
+// near x = 2.  x < 0.5 (the non-analytic part) and x beyond
 // the table use the exact evaluation.  Clenshaw: ~2 fp64 operations per term.
 #define MK_CH_N 12                         // Chebyshev terms per interval (degree 11)
 #define MK_CH_LD (MK_CH_N + 2)             // per interval: coefficients, centre, 1 / half-width

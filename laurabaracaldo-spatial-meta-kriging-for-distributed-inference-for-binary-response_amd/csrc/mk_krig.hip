@@ -70,21 +70,10 @@ int mk::kriging_buffers(mk_session* s, int n_test_all, const double* coords_test
   md.coords_test = d_ct;
   s->kbufs = {d_ct, s->d_ct_all, md.s_pred, md.s_part, md.PT, md.XK, md.w_pred, d_spt};
   {   // Matern kriging tables (k_pred_PT_matern): a bound on every subset-site to test-site distance
-    double t0 = 0.0, t1 = 0.0, t2 = 0.0, t3 = 0.0;
-    for (int t = 0; t < n_test_all; ++t) {
-      const double x = coords_test[t], y = coords_test[n_test_all + t];
-      if (t == 0 || x < t0) t0 = x;
-      if (t == 0 || x > t1) t1 = x;
-      if (t == 0 || y < t2) t2 = y;
-      if (t == 0 || y > t3) t3 = y;
-    }
+    double tb[4];
+    site_bbox(coords_test, coords_test + n_test_all, n_test_all, tb);
     std::vector<double> hs(S);
-    for (int i = 0; i < S; ++i) {
-      const double* b = s->bbox.data() + 4 * i;
-      hs[i] = n_test_all > 0 ? std::hypot(std::fmax(std::fabs(b[1] - t0), std::fabs(t1 - b[0])),
-                                          std::fmax(std::fabs(b[3] - t2), std::fabs(t3 - b[2])))
-                             : 0.0;
-    }
+    for (int i = 0; i < S; ++i) hs[i] = n_test_all > 0 ? matern_span_pt(s->bbox.data() + 4 * i, tb) : 0.0;
     HIPCHK(hipMemcpy(d_spt, hs.data(), (size_t)S * 8, hipMemcpyHostToDevice));
     md.span_pt = d_spt;
     s->span_pt_h = hs;

@@ -8,45 +8,78 @@
 using namespace mk;
 
 // ------------------------------------------------------------------ parity-test entry points
-extern "C" int mk_correlation_batched(const double* coords, int32_t S, int32_t n, const double* phi, const double* nu,
-                                      int32_t cov_model, double* R_out, int32_t device) {
-  if (!coords || !phi || !R_out || S < 1 || n < 1) return set_err(MK_E_ARG, "bad correlation arguments");
+// R (candidate route) and P^T (kriging route) of S point sets by the session's own kernels, each set a
+// one-outcome Model assembled here: theta = 0 with Unif(0, 2 phi) / Unif(0, 2 nu) supports gives exactly
+// phi and nu (logitInv(0, 0, b) = b - b/2); the border row is u = 0.  stored_tables: the Matern tables
+// as a session has them (span / span_pt by the session's expressions, k_matern_table /
+// k_matern_table_list store them, the tile workgroups load them); else the span and table pointers
+// stay null and the kernels build unbounded tables themselves.
+extern "C" int mk_correlation_cross_batched(const double* coords, int32_t S, int32_t n, const double* coords_test,
+                                            int32_t n_test, const double* phi, const double* nu, int32_t cov_model,
+                                            int32_t stored_tables, double* R_out, double* PT_out, int32_t device) {
+  if (!coords || !phi || S < 1 || n < 1 || (!R_out && !PT_out)) return set_err(MK_E_ARG, "bad correlation arguments");
+  if (PT_out && (!coords_test || n_test < 1)) return set_err(MK_E_ARG, "P^T needs test sites");
   if (cov_model != MK_COV_EXPONENTIAL && cov_model != MK_COV_MATERN) return set_err(MK_E_ARG, "bad cov_model");
   if (cov_model == MK_COV_MATERN && !nu) return set_err(MK_E_ARG, "matern needs nu");
   for (int s = 0; s < S; ++s)
     if (!(phi[s] > 0.0) || (nu && cov_model == MK_COV_MATERN && !(nu[s] > 0.0)))
       return set_err(MK_E_ARG, "phi and nu must be > 0");
   MK_ENTRY_DEVICE(device);
-  // The sampler's own candidate kernel (k_cov_candidate, which = 2: the current theta) on a
-  // one-outcome model per point set: theta = 0 with Unif(0, 2 phi) / Unif(0, 2 nu) supports gives
-  // exactly phi and nu (logitInv(0, 0, b) = b - b/2).  The border row is u = 0.
   const int n_pad = round_up(n + 1, MK_NB), nt = n_pad / MK_NB;
-  const bool matern = cov_model == MK_COV_MATERN;
+  const bool matern = cov_model == MK_COV_MATERN, stored = matern && stored_tables != 0;
   const int n_theta = matern ? 3 : 2;
+  const int nte = PT_out ? n_test : 0;
+  const int n_test_pad = round_up(std::max(nte, 1), 256);   // as kriging_buffers: the kernels write ntt * 128 columns
   DevBufs b;
   double* dc = b.get<double>((size_t)S * 2 * n_pad);
   double* dth = b.get<double>((size_t)S * n_theta);
   double* du = b.get<double>((size_t)S * n_pad);
   int* dns = b.get<int>(S);
-  int* dcur = b.get<int>(S);
-  double* dL = b.get<double>((size_t)S * 2 * n_pad * n_pad);
-  double* dr = b.get<double>((size_t)S * n * n);
-  if (!dc || !dth || !du || !dns || !dcur || !dL || !dr) return set_err(MK_E_NOMEM, "correlation alloc");
-  std::vector<double> hc((size_t)S * 2 * n_pad, 0.0);
-  for (int s = 0; s < S; ++s)
+  int* dcur = b.get<int>(S + 2);                           // [S] slots (0), then the pair list {0} and its count {1}
+  double* dL = R_out ? b.get<double>((size_t)S * 2 * n_pad * n_pad) : nullptr;
+  double* dr = R_out ? b.get<double>((size_t)S * n * n) : nullptr;
+  double* dct = PT_out ? b.get<double>((size_t)S * 2 * n_test_pad) : nullptr;
+  double* dPT = PT_out ? b.get<double>((size_t)S * n_pad * n_test_pad) : nullptr;
+  double* dspan = stored ? b.get<double>((size_t)2 * S) : nullptr;           // [S] span, [S] span_pt
+  double* dtab = stored ? b.get<double>((size_t)2 * S * MK_CH_TAB) : nullptr;   // [S] chtab, [S] chtab_p
+  if (!dc || !dth || !du || !dns || !dcur || (R_out && (!dL || !dr)) || (PT_out && (!dct || !dPT)) ||
+      (stored && (!dspan || !dtab)))
+    return set_err(MK_E_NOMEM, "correlation alloc");
+  std::vector<double> hc((size_t)S * 2 * n_pad, 0.0), hct, hspan((size_t)2 * S, 0.0);
+  if (PT_out) hct.assign((size_t)S * 2 * n_test_pad, 0.0);
+  for (int s = 0; s < S; ++s) {
+    const double* cs = coords + (size_t)s * 2 * n;
     for (int r = 0; r < n; ++r) {
-      hc[(size_t)s * 2 * n_pad + r] = coords[(size_t)s * 2 * n + r];
-      hc[(size_t)s * 2 * n_pad + n_pad + r] = coords[(size_t)s * 2 * n + n + r];
+      hc[(size_t)s * 2 * n_pad + r] = cs[r];
+      hc[(size_t)s * 2 * n_pad + n_pad + r] = cs[n + r];
     }
-  std::vector<int> hn(S, n);
+    double bb[4], tb[4];
+    site_bbox(cs, cs + n, n, bb);
+    hspan[s] = matern_span(bb);
+    if (PT_out) {
+      const double* ts = coords_test + (size_t)s * 2 * n_test;
+      for (int t = 0; t < n_test; ++t) {
+        hct[(size_t)s * 2 * n_test_pad + t] = ts[t];
+        hct[(size_t)s * 2 * n_test_pad + n_test_pad + t] = ts[n_test + t];
+      }
+      site_bbox(ts, ts + n_test, n_test, tb);
+      hspan[S + s] = matern_span_pt(bb, tb);
+    }
+  }
+  std::vector<int> hn(S, n), hcur(S + 2, 0);
+  hcur[S + 1] = 1;
   HIPCHK(hipMemcpy(dc, hc.data(), hc.size() * 8, hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(dns, hn.data(), (size_t)S * 4, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(dcur, hcur.data(), hcur.size() * 4, hipMemcpyHostToDevice));
   HIPCHK(hipMemset(dth, 0, (size_t)S * n_theta * 8));
   HIPCHK(hipMemset(du, 0, (size_t)S * n_pad * 8));
-  HIPCHK(hipMemset(dcur, 0, (size_t)S * 4));
+  if (PT_out) HIPCHK(hipMemcpy(dct, hct.data(), hct.size() * 8, hipMemcpyHostToDevice));
+  if (stored) HIPCHK(hipMemcpy(dspan, hspan.data(), hspan.size() * 8, hipMemcpyHostToDevice));
   MatSet ms{};
   ms.L = dL; ms.cur = dcur; ms.ld = n_pad; ms.nt = nt; ms.q = 1;
   const int ntri_tiles = nt * (nt + 1) / 2;
+  const int* d_list = dcur + S;
+  const int* d_count = dcur + S + 1;
   for (int s = 0; s < S; ++s) {
     Model md{};
     md.S = 1; md.q = 1; md.p = 0; md.n_pad = n_pad; md.Np = n_pad; md.nt = nt; md.ntri = 1; md.n_theta = n_theta;
@@ -58,16 +91,49 @@ extern "C" int mk_correlation_batched(const double* coords, int32_t S, int32_t n
     md.coords = dc + (size_t)s * 2 * n_pad;
     md.theta = dth + (size_t)s * n_theta;
     md.u = du + (size_t)s * n_pad;
-    MatSet mv = ms;
-    mv.L = dL + (size_t)s * 2 * n_pad * n_pad;
-    mv.cur = dcur + s;
-    MK_LAUNCH(cov_candidate_kernel(cov_model), dim3(xcd_grid_h(1, ntri_tiles)), dim3(256), 0, 0, md, mv, 0, 1,
-                       2, 0, nullptr, nullptr);
+    if (stored) {
+      md.span = dspan + s;
+      md.chtab = dtab + (size_t)s * MK_CH_TAB;
+      if (PT_out) {
+        md.span_pt = dspan + S + s;
+        md.chtab_p = dtab + (size_t)(S + s) * MK_CH_TAB;
+      }
+    }
+    if (R_out) {
+      MatSet mv = ms;
+      mv.L = dL + (size_t)s * 2 * n_pad * n_pad;
+      mv.cur = dcur + s;
+      if (stored) MK_LAUNCH(k_matern_table, dim3(1), dim3(256), 0, 0, md, 0, 1, 2, 0, nullptr, nullptr);
+      MK_LAUNCH(cov_candidate_kernel(cov_model), dim3(xcd_grid_h(1, ntri_tiles)), dim3(256), 0, 0, md, mv, 0, 1,
+                         2, 0, nullptr, nullptr);
+    }
+    if (PT_out) {
+      md.n_test = n_test; md.n_test_pad = n_test_pad; md.ntt = n_test_pad / MK_NB;
+      md.coords_test = dct + (size_t)s * 2 * n_test_pad;
+      md.PT = dPT + (size_t)s * n_pad * n_test_pad;
+      if (matern) {
+        if (stored) MK_LAUNCH(k_matern_table_list, dim3(1), dim3(256), 0, 0, md, d_list, d_count);
+        MK_LAUNCH(k_pred_PT_matern, dim3(n_pad / MK_PT_RB), dim3(256), 0, 0, md, d_list, d_count);
+      } else {
+        MK_LAUNCH(pred_PT_kernel(cov_model), dim3(n_pad), dim3(256), 0, 0, md, d_list, d_count);
+      }
+    }
   }
-  MK_LAUNCH(k_extract_candidate, dim3(2048), dim3(256), 0, 0, ms, n, S, dr);
+  if (R_out) MK_LAUNCH(k_extract_candidate, dim3(2048), dim3(256), 0, 0, ms, n, S, dr);
   HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpy(R_out, dr, (size_t)S * n * n * 8, hipMemcpyDeviceToHost));
+  if (R_out) HIPCHK(hipMemcpy(R_out, dr, (size_t)S * n * n * 8, hipMemcpyDeviceToHost));
+  if (PT_out) {   // rows k < n, columns t < n_test of every set's [n_pad][n_test_pad]
+    for (int s = 0; s < S; ++s)
+      HIPCHK(hipMemcpy2D(PT_out + (size_t)s * n * n_test, (size_t)n_test * 8, dPT + (size_t)s * n_pad * n_test_pad,
+                         (size_t)n_test_pad * 8, (size_t)n_test * 8, n, hipMemcpyDeviceToHost));
+  }
   return 0;
+}
+
+extern "C" int mk_correlation_batched(const double* coords, int32_t S, int32_t n, const double* phi, const double* nu,
+                                      int32_t cov_model, double* R_out, int32_t device) {
+  if (!R_out) return set_err(MK_E_ARG, "bad correlation arguments");
+  return mk_correlation_cross_batched(coords, S, n, nullptr, 0, phi, nu, cov_model, 0, R_out, nullptr, device);
 }
 
 extern "C" int mk_cholesky_batched(const double* A, int32_t S, int32_t n, double* L_out, double* logdet_out,

@@ -21,6 +21,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <algorithm>
+#include <cmath>
 #include <cstdlib>
 #include <string>
 #include <utility>
@@ -55,6 +56,25 @@ static inline int round_up(int a, int b) { return (a + b - 1) / b * b; }
 static inline int env_int(const char* name, int dflt) {
   const char* v = std::getenv(name);
   return (v && *v) ? std::atoi(v) : dflt;
+}
+
+// Ranges of the Matern Chebyshev tables (Model::span, Model::span_pt), shared by the sessions and the
+// parity entry mk_correlation_cross_batched: b = xmin xmax ymin ymax of n sites (zeros when n = 0),
+// the bounding-box diagonal of a subset's sites, and the bound on every distance from a subset's
+// sites (box b) to the test sites (box t).
+static inline void site_bbox(const double* x, const double* y, int n, double* b) {
+  b[0] = b[1] = b[2] = b[3] = 0.0;
+  for (int r = 0; r < n; ++r) {
+    if (r == 0 || x[r] < b[0]) b[0] = x[r];
+    if (r == 0 || x[r] > b[1]) b[1] = x[r];
+    if (r == 0 || y[r] < b[2]) b[2] = y[r];
+    if (r == 0 || y[r] > b[3]) b[3] = y[r];
+  }
+}
+static inline double matern_span(const double* b) { return std::hypot(b[1] - b[0], b[3] - b[2]); }
+static inline double matern_span_pt(const double* b, const double* t) {
+  return std::hypot(std::fmax(std::fabs(b[1] - t[0]), std::fabs(t[1] - b[0])),
+                    std::fmax(std::fabs(b[3] - t[2]), std::fabs(t[3] - b[2])));
 }
 
 constexpr int NKSTAT = 19;

@@ -571,6 +571,38 @@ def correlation_batched(coords, phi, nu=None, cov_model="exponential", device=0)
     return np.ascontiguousarray(np.transpose(out, (0, 2, 1)))   # column-major -> (S, n, n) row-major
 
 
+def correlation_cross_batched(coords, phi, nu=None, cov_model="exponential", coords_test=None, stored_tables=False,
+                              want_R=True, device=0):
+    """(R, PT) of a batch of point sets by the session's own kernels (mk_correlation_cross_batched): R (S, n, n)
+    between the sites coords (S, n, 2) by the candidate kernel (None unless want_R), PT (S, n, n_test) from
+    them to the sets' own test sites coords_test (S, n_test, 2) by the kriging kernels (None without test
+    sites).  stored_tables: the Matern Chebyshev tables as a session has them -- bounded by phi x the sites'
+    extent, stored by their own kernels and loaded by the tile workgroups; else built in the kernels,
+    unbounded (correlation_batched's configuration)."""
+    lib = _lib.load()
+    coords = np.asarray(coords, float)
+    S, n, _ = coords.shape
+    c = _f64(np.stack([coords[i].ravel(order="F") for i in range(S)]))
+    ph = _f64(np.broadcast_to(np.asarray(phi, float), (S,)))
+    nv = None if nu is None else _f64(np.broadcast_to(np.asarray(nu, float), (S,)))
+    ct, n_test, PT = None, 0, None
+    if coords_test is not None:
+        coords_test = np.asarray(coords_test, float)
+        if coords_test.ndim != 3 or coords_test.shape[0] != S or coords_test.shape[2] != 2:
+            raise ValueError("error: coords_test is (S, n_test, 2), one set of test sites per point set")
+        n_test = coords_test.shape[1]
+        ct = _f64(np.stack([coords_test[i].ravel(order="F") for i in range(S)]))
+        PT = np.zeros((S, n, n_test))
+    R = np.zeros((S, n, n)) if want_R else None
+    check(lib.mk_correlation_cross_batched(dptr(c), S, n, dptr(ct) if ct is not None else None, int(n_test), dptr(ph),
+                                           dptr(nv) if nv is not None else None, COV_MODELS[cov_model],
+                                           int(bool(stored_tables)), dptr(R) if want_R else None,
+                                           dptr(PT) if PT is not None else None, int(device)))
+    if want_R:
+        R = np.ascontiguousarray(np.transpose(R, (0, 2, 1)))   # column-major -> (S, n, n) row-major
+    return R, PT
+
+
 def cholesky_batched(A, inverse=False, device=0):
     """Lower Cholesky factors, log-determinants (and inverses) of a batch of SPD matrices (S, n, n)."""
     lib = _lib.load()

@@ -8,8 +8,9 @@ test site t (layouts: oracle/spmvglm.py fit_subset section 7), per outcome h
     draw_t = A (m_t + sd_t z*_t),         z* = oracle/philox.py predict_normal(key, site q + h, iteration)
 in np.longdouble (80-bit where the platform has it): distances, exp, the Cholesky factor
 (linalg_ref.chol_longdouble), X = L^-1 P', z = L^-1 u, s = colsum(X^2), m = X' z, lambda_t = R^-1 rho_t.
-Matern correlations are float64 scipy.special.kv promoted (1 at d = 0).  Beside it the same draw in
-float64 through LAPACK with the oracle's own expressions: the error scale e_L.
+Matern correlations are matern_ref.rho_longdouble (a longdouble quadrature, no kv; 1 at d = 0), so the
+reference is 80-bit throughout.  Beside it the same draw in float64 through LAPACK with the oracle's own
+expressions: the error scale e_L.
 
 The bounds are derived, not measured (eps = 2^-52, N = n_s + 1 the order the device factors, kappa =
 kappa_2(R_h), per site t and outcome h, then the largest over h):
@@ -29,7 +30,8 @@ kappa_2(R_h), per site t and outcome h, then the largest over h):
   phi-interpolated arms add |A|_inf |z*| tol / (sd_ref + sqrt(tol)) to both bars, tol = 1e-10
       (MK_KRIG_CHEB_TOL's default, mk_krig.hip cheb_tol: the interpolant's checked error in s).
   Matern adds 1e-13 kappa |rho_t| |lambda_t| to B_s and 1e-13 kappa |lambda_t| |u_h| to B_m: the
-      device's tables and scipy's kv agree to 1e-13 relative (mk_corr.hpp)."""
+      device's Matern is within 1e-13 relative of the longdouble reference (tests/test_gpu_matern.py
+      asserts it element by element, beside the rounding of x = phi d that N eps covers here)."""
 import numpy as np
 import scipy.linalg as sla
 
@@ -37,12 +39,13 @@ from oracle import philox
 from oracle import spmvglm as om
 
 from linalg_ref import EPS, chol_longdouble
+from matern_ref import rho_longdouble
 
 LD = np.longdouble
 RATIO = 16.0          # the comparative bar's margin (module docstring)
 REGULAR_SD = 0.05     # sites with sd_ref below this get the hard bar only
 CHEB_TOL = 1e-10      # MK_KRIG_CHEB_TOL's default
-KV_REL = 1e-13        # the device's Matern tables against scipy's kv (mk_corr.hpp)
+KV_REL = 1e-13        # the device's Matern against matern_ref.rho_longdouble: asserted by tests/test_gpu_matern.py
 OFFSETS = (0.0, 1e-9, 1e-6, 1e-3)
 
 
@@ -55,10 +58,14 @@ def dist_longdouble(c1, c2):
 
 
 def corr_longdouble(d, phi, nu, matern):
-    """rho(d) in longdouble; Matern: float64 kv (the oracle's correlation) promoted, 1 at d = 0."""
+    """rho(d) in longdouble; Matern: matern_ref.rho_longdouble at x = phi d, 1 at d = 0."""
     if not matern:
         return np.exp(-LD(phi) * d)
-    return om.correlation(np.asarray(d, dtype=np.float64), float(phi), float(nu), om.COV_MATERN).astype(LD)
+    x = LD(phi) * np.asarray(d, dtype=LD)
+    out = np.ones(x.shape, dtype=LD)
+    m = x > 0
+    out[m] = rho_longdouble(x[m], nu)
+    return out
 
 
 def forward_solve(L, B):

@@ -84,6 +84,23 @@ def test_a_test_site_on_an_observed_site_and_one_far_away():
     assert not ref["regular"][4] and ref["regular"][9]
 
 
+def test_matern_arm_is_the_longdouble_reference():
+    """corr_longdouble's Matern arm is matern_ref.rho_longdouble (tests/test_matern_ref.py), not float64 kv
+    promoted: at nu = 1/2 it is exp(-phi d) to longdouble precision, which float64 cannot be; it is 1 at
+    d = 0; and the oracle's kv stays within 1e-11 of it at a general nu."""
+    c, ct, _ = _small()
+    ct = ct.copy()
+    ct[4] = c[17]
+    d = kr.dist_longdouble(ct, c)
+    r = kr.corr_longdouble(d, 6.3, 0.5, True)
+    assert r.dtype == LD and r[4, 17] == 1
+    e = np.exp(-LD(6.3) * d)
+    assert float(np.max(np.abs(r - e) / e)) <= 64 * LD_EPS
+    r = kr.corr_longdouble(d, 6.3, 1.3, True)
+    o = om.correlation(d.astype(np.float64), 6.3, 1.3, om.COV_MATERN)
+    assert float(np.max(np.abs(o.astype(LD) - r) / r)) <= 1e-11
+
+
 @pytest.mark.parametrize("q", [1, 2])
 def test_one_philox_slot_per_site_outcome_and_iteration(q):
     """fit_subset (the CPU oracle) krigs four far sites with global indices 0, 3, 256 and 260: there
