@@ -202,7 +202,9 @@ int mk_session_tile_grids_wp(mk_session* s, int32_t t0, double* out_w, double* o
  * k_score_cols / k_score_finish -- launches and ms, always timed, 0 launches unless validation data were
  * attached; 17 the posterior-map launches k_map_cols -- launches and ms, always timed, 0 launches unless
  * maps were asked for; 18 the cross-outcome launches k_quantiles_pair / k_pair_cols -- launches (one per
- * kernel) and ms, always timed, 0 launches unless pairs were asked for).  Flops are algorithmic, not executed: GEMM tiles 2 m n k, the diagonal tile's
+ * kernel) and ms, always timed, 0 launches unless pairs were asked for; 19 the areal-prediction launches
+ * k_region_cov / k_region_draw per kept state and k_quantiles / k_map_cols per replay -- launches (one per
+ * kernel) and ms, always timed, 0 launches unless regions were attached).  Flops are algorithmic, not executed: GEMM tiles 2 m n k, the diagonal tile's
  * update as a SYRK, solves and inverse products over their triangles.  mk_session_profile(s, enable)
  * before mk_session_run: enable 0 = off, 1 = every kind, otherwise a mask with bit (1 + kind) per kind
  * bracketed (e.g. 2 << 0 = the panel update only; fewer events, less overhead). */
@@ -543,6 +545,80 @@ int mk_meta_fit_pairs(const mk_problem* prob, const mk_config* cfg, const int32_
                       mk_progress_fn progress, void* user, mk_outputs* out, mk_combined* comb, mk_diagnostics* diag,
                       mk_criteria* crit, const mk_validation* val, mk_scores* scores, const mk_map_spec* spec,
                       mk_maps* maps, const mk_pair_spec* pair_spec, mk_pairs* pairs);
+
+/* ---- areal prediction: the prevalence of a region from joint kriging draws ----
+ * The prevalence of a district is the (population-weighted) mean of p(y = 1) over the test sites inside it.
+ * The per-site draws above are marginal across sites: averaging them gives the right mean and too small a
+ * spread, because kriging errors at neighbouring sites are strongly correlated.  Here the draws of a region's
+ * sites are joint, per kept state, and only their weighted mean -- one scalar per (state, region, outcome) --
+ * leaves the replay.
+ * A region spec partitions the session's current test sites, in their order, into G contiguous runs:
+ * offsets[0 .. G] with offsets[0] = 0, offsets[G] = n_test, strictly increasing; m_g = offsets[g+1] -
+ * offsets[g] <= MK_REGION_MAXM; one weight per test site (NULL: all 1), finite and >= 0 with a positive sum in
+ * every region; up to MK_MAP_MAXT thresholds.  The host normalises the weights once, omega_i = weight_i / (the
+ * sum of the region's weights, added in index order); the device only sees omega.
+ * For subset s, kept state k of the window (iteration it), outcome h and region g with sites t_1 < .. < t_m
+ * (global test-site indices):
+ *   mean_i,h = X_h,t_i . z_h over rows < n_s                                  (k_pred_draw's mean)
+ *   S_h      = R_h(g,g) - X_g' X_g, lower triangle, rows < n_s of X only; R_h(g,g) the model's own
+ *              correlation (exponential or Matern, at the state's phi_h, nu_h) between the region's sites,
+ *              unit diagonal
+ *   L_h      = the Cholesky factor of S_h in site order; a pivot that is not > MK_REGION_PIVOT_TOL zeroes
+ *              that column of L (the site is conditionally determined by the data and the sites before it)
+ *              and flags the factor
+ *   zeta_i,h = predict_normal(key_s, t_i q + h, it): the Philox word of the marginal draw of that site,
+ *              outcome and state
+ *   v_i,h    = mean_i,h + sum_{j <= i} L_h[i,j] zeta_j,h, j ascending
+ *   w*_i,a   = sum_h v_i,h A[a,h]                                              (k_pred_draw's order)
+ *   p_i,a    = pred_prob of column t_i q + a                                   (the p draws' expression)
+ *   r_g,a    = sum_i omega_i p_i,a, i ascending: one draw of the regional prevalence
+ * Region column c = g q + a; C3 = G q.  A region of one site reproduces that site's p_pred_samples (to the
+ * summation order of its kriging variance); the first site of every region keeps its marginal law.  The
+ * draws depend only on (seed, global subset index, test-site index): not on sharding or stream groups.
+ * Outputs per subset:
+ *   region_samples  C3 x kept column-major, like p_pred_samples
+ *   region_predict  200 x C3: the type-7 quantiles of the draws (the p grids' kernel)
+ *   planes          C3 x (2 + J): mean, sd, exc_1..J -- the maps' formulas on the draws, in time order, the
+ *                   exceedance strict; a non-finite draw makes the column's planes NaN
+ *   singular        int32 [C3]: the kept states of the window whose factor for (region g, outcome a) was
+ *                   flagged, at column g q + a
+ * The regions need a session created with predict_tile > 0 whose tile holds every test site: the joint
+ * covariance is formed from X = W P^T, which only the exact tiled replay has in HBM.  While regions are
+ * attached the phi-interpolated replay is not used, so the tile's other outputs (grids, draws, maps, pairs,
+ * scores) are the exact replay's: they agree with the interpolated ones to the documented 1e-8, not bit for
+ * bit.  The fused (in-chain) route, the node call, regions above MK_REGION_MAXM sites or across tiles, and a
+ * thinned replay are not covered. */
+#define MK_REGION_MAXM 128          /* sites per region at most */
+#define MK_REGION_PIVOT_TOL 1e-12   /* a pivot of S_h that is not above this zeroes its column */
+typedef struct mk_region_spec {
+  int32_t n_regions;           /* G */
+  const int32_t* offsets;      /* [G + 1] */
+  const double* weights;       /* [n_test], or NULL: every site weighs 1 */
+  int32_t n_thresholds;        /* J */
+  const double* thresholds;
+} mk_region_spec;
+typedef struct mk_regions {           /* caller-allocated, any pointer may be NULL */
+  double* region_predict;      /* [n_subsets] x (200 x C3) */
+  double* planes;              /* [n_subsets] x (C3 x (2 + J)) */
+  double* region_samples;      /* [n_subsets] x (C3 x kept) */
+  int32_t* singular;           /* [n_subsets] x C3 */
+  double* timing_ms;           /* [3]: the region launches' time since the attach -- covariance and factor,
+                                  draws, grids and planes (HIP events; kernel kind 19 holds their sum) */
+} mk_regions;
+/* Attach a region spec to the session's current test sites (NULL detaches and frees).  Everything is checked
+ * on the host before any device is touched, each failure MK_E_ARG naming the offending index: bad offsets, a
+ * region above MK_REGION_MAXM, a bad weight or threshold, two sites of one region at identical coordinates;
+ * no test sites, no x_test or no recorded samples; a session that was not created with predict_tile > 0 (the
+ * message names the remedy); more test sites than the session's tile (mk_session_predict_tile).  The session
+ * takes its buffers here and only here: per (subset, outcome) sum_g m_g^2 doubles of factors, per subset C3
+ * doubles per kept state, and the grids and planes; MK_E_NOMEM names the remedies.  While attached, every
+ * tile replay also makes the regional draws, from the same replay and over its kept window.
+ * mk_session_set_test_sites detaches.  Nothing is launched or allocated for the regions unless they were
+ * attached. */
+int mk_session_set_regions(mk_session* s, const mk_region_spec* spec);
+/* After all iterations: copies the buffers out.  MK_E_ARG if the tile has not been replayed over the current
+ * kept window since the regions were attached. */
+int mk_session_regions(mk_session* s, mk_regions* out);
 
 /* ---- combine (MK.R:123-133): out = (grid_1 + ... + grid_K) / K, sequential order ---- */
 int mk_combine(const double* grids, int32_t K, int64_t grid_len, double* out, int32_t device);

@@ -34,6 +34,8 @@ N_MAP_BASE = 4         # MK_N_MAP_BASE: the planes before the exceedances, in MA
 MAP_BASE_NAMES = ["w_mean", "w_sd", "p_mean", "p_sd"]
 N_PAIR_BASE = 6        # MK_N_PAIR_BASE: the pair planes before joint_1..J, in PAIR_BASE_NAMES' order
 PAIR_BASE_NAMES = ["both_mean", "both_sd", "diff_mean", "diff_sd", "corr", "a_gt_b"]
+REGION_MAXM = 128      # MK_REGION_MAXM: sites per region at most
+REGION_BASE_NAMES = ["mean", "sd"]     # the region planes before exc_1..J
 
 _dp = ctypes.POINTER(ctypes.c_double)
 _ip = ctypes.POINTER(ctypes.c_int32)
@@ -115,6 +117,15 @@ class Pairs(ctypes.Structure):
                 ("combined_diff", _dp)]
 
 
+class RegionSpec(ctypes.Structure):
+    _fields_ = [("n_regions", ctypes.c_int32), ("offsets", _ip), ("weights", _dp), ("n_thresholds", ctypes.c_int32),
+                ("thresholds", _dp)]
+
+
+class Regions(ctypes.Structure):
+    _fields_ = [("region_predict", _dp), ("planes", _dp), ("region_samples", _dp), ("singular", _ip), ("timing_ms", _dp)]
+
+
 # int (*mk_progress_fn)(void* user, int32_t iterations, int32_t n_samples)
 PROGRESS_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32)
 
@@ -137,6 +148,8 @@ EXPORTS = {
                                          ctypes.POINTER(PairSpec), ctypes.POINTER(Pairs)]),
     "mk_session_set_pairs": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(PairSpec)]),
     "mk_session_pairs": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(Pairs)]),
+    "mk_session_set_regions": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(RegionSpec)]),
+    "mk_session_regions": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(Regions)]),
     "mk_session_set_maps": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(MapSpec)]),
     "mk_session_maps": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(Maps)]),
     "mk_map_grid": (ctypes.c_int, [_dp, ctypes.c_int32, ctypes.c_int64, _dp, ctypes.c_int32, _dp, ctypes.c_int32]),

@@ -86,6 +86,7 @@ int mk::kriging_buffers(mk_session* s, int n_test_all, const double* coords_test
     hct[npa + t] = coords_test[n_test_all + t];
   }
   HIPCHK(hipMemcpy(s->d_ct_all, hct.data(), hct.size() * 8, hipMemcpyHostToDevice));
+  s->ct_h.assign(coords_test, coords_test + (size_t)2 * n_test_all);
   // fused kriging reads every site from d_ct ([2][n_test_pad]); tiled mode fills it per tile
   if (!s->tiled) HIPCHK(hipMemcpy(d_ct, hct.data(), hct.size() * 8, hipMemcpyHostToDevice));
   s->all.md = s->md;
@@ -104,6 +105,7 @@ static int tile_sinks(mk_session* s, int t0, int n_kept, int Ct) {
   if (!rc && s->val.on) rc = tile_scores(s, t0, n_kept, Ct);
   if (!rc && s->maps.on) rc = tile_maps(s, t0, n_kept, Ct);
   if (!rc && s->pairs.on) rc = tile_pairs(s, t0, n_kept, Ct);
+  if (!rc && s->regions.on) rc = tile_regions(s, t0, n_kept, Ct);   // fed inside the replay loop, not from md.w_pred
   return rc;
 }
 
@@ -114,6 +116,7 @@ static void detach_sinks(mk_session* s) {
   validation_detach(s);
   maps_detach(s);
   pairs_detach(s);
+  regions_detach(s);
 }
 
 extern "C" int mk_session_set_test_sites(mk_session* s, int32_t n_test, const double* coords_test) {
@@ -478,6 +481,7 @@ static int predict_tile_cheb(mk_session* s, int t0, double* dq, mk_outputs* o, d
   Model& md = s->md;
   const int force_n = cheb_mode();
   if (force_n == 0 || md.cov_model != MK_COV_EXPONENTIAL) return MK_CHEB_EXACT;
+  if (s->regions.on) return MK_CHEB_EXACT;   // the joint covariance of a region needs X, which only the exact replay forms
   const int S = s->S, q = s->q, SQ = S * q, nth = md.n_theta, n_pad = md.n_pad;
   const int k_lo = s->win_lo, n_kept = s->win_n < 0 ? md.n_kept : s->win_n;
   if (n_kept < 1 || (int)s->span_pt_h.size() != S) return MK_CHEB_EXACT;
@@ -657,6 +661,10 @@ int mk::predict_tile(mk_session* s, int t0, double* dq, mk_outputs* o, double* d
     if (!s->d_run_start && (rc = s->alloc(&s->d_run_start, (size_t)S))) return rc;
     HIPCHK(hipMemsetAsync(s->d_run_start, 0, (size_t)S * sizeof(int), st));
   }
+  if (s->regions.on) {
+    const int rc = regions_begin(s, t0, Tc, n_kept);
+    if (rc) return rc;
+  }
   for (int j = 0; j < n_kept; ++j) {
     const int k = k_lo + j;   // kept state k = iteration kept0 + k
     mt.theta = md.kth + (long)k * S * md.n_theta;
@@ -680,6 +688,10 @@ int mk::predict_tile(mk_session* s, int t0, double* dq, mk_outputs* o, double* d
     launch_pred_refresh(s, g);
     if (!runs) MK_LAUNCH(k_pred_draw, dim3(S * per), dim3(256), 0, st, mt, md.kept0 + k, j);
     HIPCHK(hipGetLastError());
+    if (s->regions.on) {   // X is current for every subset: this state's factors where phi changed, then its regional draws
+      const int rc = regions_state(s, g, mt, md.kept0 + k, j, n_kept);
+      if (rc) return rc;
+    }
   }
   if (runs && n_kept > 0) {   // every subset's last run
     MK_LAUNCH(k_pred_draw_runs, dim3(S * per), dim3(256), 0, st, mt, md.kz, md.kA, k_lo, (const int*)nullptr,

@@ -99,6 +99,14 @@ int session_maps(mk_session* s, int t0, int n, long Ct, double* planes) {
 }
 }  // namespace
 
+int mk::launch_map_values(hipStream_t st, const double* data, long subset_stride, long row_stride, int n, int n_cols,
+                          int S, const MapThr& th, double* planes) {
+  MK_LAUNCH(k_map_cols<true>, dim3((unsigned)((n_cols + 255) / 256), S), dim3(256), 0, st, data, subset_stride, row_stride,
+            1L, n, n_cols, ProbSrc{}, th, 0L, (long)n_cols, planes);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
 int mk::map_thresholds(const double* thresholds, int J, MapThr* th) {
   if (J < 0 || J > MK_MAP_MAXT)
     return set_err(MK_E_ARG, "posterior maps: n_thresholds = " + std::to_string(J) + " is outside 0 .. " +

@@ -11,8 +11,9 @@
 //   mk_scores.hip    held-out validation (log score, Brier, error rate): the kernels, the entry points
 //   mk_maps.hip      posterior maps (mean, sd, exceedance of p(y = 1)): the kernel, the entry points
 //   mk_pairs.hip     cross-outcome prediction (co-occurrence and contrast of two outcomes): the kernels, the entry points
+//   mk_regions.hip   areal prediction (regional prevalence from joint kriging draws): the kernels, the entry points
 //
-// What the five result sinks above share is here and in mk_tilefill.hpp: EventTimer (their launches' price),
+// What the six result sinks above share is here and in mk_tilefill.hpp: EventTimer (their launches' price),
 // TileFill (which tiles a tiled session's buffer holds, over which kept window), results_entry (the checks a
 // results call starts with), upload_col_chunks (the stand-alone grid entries) and sink_nomem.  The list of
 // sinks a tile replay fills and mk_session_set_test_sites detaches is in mk_krig.hip (tile_sinks, detach_sinks).
@@ -30,6 +31,7 @@
 #include "mk_kernels.hpp"
 #include "mk_internal.hpp"
 #include "mk_tilefill.hpp"
+#include "mk_regionspec.hpp"
 
 namespace mk {
 int set_err(int code, const std::string& msg);   // mk_api.hip: sets mk_last_error(), returns code
@@ -77,7 +79,7 @@ static inline double matern_span_pt(const double* b, const double* t) {
                     std::fmax(std::fabs(b[3] - t[2]), std::fabs(t[3] - b[2])));
 }
 
-constexpr int NKSTAT = 19;
+constexpr int NKSTAT = 20;
 // KS_CHOL_UPDATE: the 128-tile panel-update launches (k_chol_update<128>); KS_CHOL_UPDATE_SUB:
 // the 64- / 32-sub-tile ones (small grids).  Together: the roofline kernel k_chol_update.
 // KS_UPDATE_BUSY: both, with the time of launches that overlap (the split schedule's bulk and
@@ -87,7 +89,7 @@ constexpr int NKSTAT = 19;
 // KS_COV: the candidates' covariance assembly (k_cov_candidate, with k_matern_table for Matern).
 enum { KS_CHOL_UPDATE = 0, KS_CHOL_DIAG, KS_CHOL_TRSM, KS_SWEEP, KS_LAUUM, KS_ITER, KS_INV, KS_CHOL_UPDATE_SUB,
        KS_UPDATE_BUSY, KS_PRED_VAR, KS_COV, KS_SWEEP_FALLBACK, KS_KRIG_CHEB, KS_KRIG_FALLBACK, KS_DIAG, KS_CRIT,
-       KS_SCORE, KS_MAPS, KS_PAIRS };
+       KS_SCORE, KS_MAPS, KS_PAIRS, KS_REGIONS };
 // KS_KRIG_CHEB: tiles kriged by phi interpolation (predict_tile_cheb): launches = tiles, flops = exact
 // s evaluations (one per (subset, outcome) pair and node or check point), total_ms = the largest check
 // difference seen over all pairs and sites (not a time).  KS_KRIG_FALLBACK: tiles whose check failed
@@ -106,6 +108,9 @@ enum { KS_CHOL_UPDATE = 0, KS_CHOL_DIAG, KS_CHOL_TRSM, KS_SWEEP, KS_LAUUM, KS_IT
 // KS_PAIRS: the cross-outcome launches (k_quantiles_pair and k_pair_cols per tile replay of a tiled session,
 // what mk_session_pairs is asked for of a fused one; launches counts kernels), bracketed by events whether or
 // not the profiler is on; none are made unless pairs were asked for.
+// KS_REGIONS: the areal-prediction launches (k_region_cov per kept state whose dirty list may hold a pair,
+// k_region_draw per kept state, then k_quantiles and k_map_cols per tile replay; launches counts kernels),
+// bracketed by events whether or not the profiler is on; none are made unless regions were attached.
 // KS_SWEEP_FALLBACK: launches = (subset, iteration) sweeps k_sweep_mg refused admission and its
 // k_sweep fallback ran (counted on the device, read at the end of every mk_session_run; no timing).
 
@@ -294,6 +299,29 @@ struct Pairs {
   TileFill fill;              // tiled: the tiles filled since the pairs were attached
 };
 
+// mk_regions.hip.  Areal prediction (mk_session_set_regions): the plan in HBM, the packed factors of every
+// (pair, region) as the replay last refreshed them, and the buffers the replay and tile_regions fill
+// (allocated when regions are attached, never otherwise).
+struct Regions {
+  bool on = false;
+  MapThr th{};
+  RegionPlan plan;            // host copy (offsets, omega, factor offsets)
+  int C3 = 0;                 // region columns G q
+  int* offsets = nullptr;     // [G + 1]
+  long* foff = nullptr;       // [G + 1]
+  double* omega = nullptr;    // [n_test_all]
+  double* L = nullptr;        // [S q][foff[G]]: region g's factor m_g x m_g column-major at foff[g]
+  int* flag = nullptr;        // [S q][G]: 1 where that factor met a pivot that is not > MK_REGION_PIVOT_TOL
+  double* draws = nullptr;    // [S][n][C3], n the replayed window (room for every kept state)
+  int* singular = nullptr;    // [S][C3]
+  double* grids = nullptr;    // [S][C3][200]
+  double* planes = nullptr;   // [S][2 + J][C3]
+  TileFill fill;
+  struct Ev { int part; hipEvent_t a, b; long launches; };
+  std::vector<Ev> pending;    // events of the launches inside the replay loop, priced by tile_regions
+  double ms[3] = {0.0, 0.0, 0.0};   // since the attach: covariance and factor | draws | grids and planes
+};
+
 }  // namespace mk
 
 struct mk_session {
@@ -334,6 +362,8 @@ struct mk_session {
   mk::Validation val;
   mk::Maps maps;
   mk::Pairs pairs;
+  mk::Regions regions;
+  std::vector<double> ct_h;       // the current test sites on the host, x then y (the regions' coincidence check)
   mk_diagnostics diag_sink{};           // mk_session_set_diagnostics: filled by every tile replay while diag_on
   bool diag_on = false;
   hipError_t launch_err = hipSuccess;   // first failed kernel launch of a run
@@ -554,6 +584,10 @@ void maps_detach(mk_session* s);
 // thresholds[0 .. J) into th (the slots past J at +inf); MK_E_ARG naming the index of a non-finite value, or J
 // when it is outside 0 .. MK_MAP_MAXT.  Touches no device.
 int map_thresholds(const double* thresholds, int J, MapThr* th);
+// k_map_cols in its values form on values already in HBM (mk_map_grid's kernel; the regional draws): state k of
+// column c of subset s is data[s * subset_stride + k * row_stride + c]; planes [S][2 + J][n_cols].  Not waited for.
+int launch_map_values(hipStream_t st, const double* data, long subset_stride, long row_stride, int n, int n_cols, int S,
+                      const MapThr& th, double* planes);
 
 // ---- mk_pairs.hip
 // The pairs' share of tile [t0, ..): the grids and planes of the tile's pair columns, from the draws in
@@ -561,5 +595,18 @@ int map_thresholds(const double* thresholds, int J, MapThr* th);
 int tile_pairs(mk_session* s, int t0, int n_kept, int Ct);
 // Frees the pair buffers and forgets the thresholds (mk_session_set_test_sites; a NULL spec).
 void pairs_detach(mk_session* s);
+
+// ---- mk_regions.hip
+// The exact tiled replay's hooks while regions are attached.  regions_begin: before the first kept state of
+// tile [t0, t0 + Tc) (clears the flagged-factor counts; MK_E_ARG unless the tile holds every test site).
+// regions_state: after launch_pred_refresh of window state j (iteration iter) -- the covariances and factors
+// of the pairs on g's dirty list, then that state's regional draws of every subset.
+int regions_begin(mk_session* s, int t0, int Tc, int n_kept);
+int regions_state(mk_session* s, Group& g, const Model& mt, int iter, int j, int n_kept);
+// The regions' share of a tile replay: the grids and planes of the regional draws the replay left, timed as
+// KS_REGIONS.  Returns after the stream is idle.
+int tile_regions(mk_session* s, int t0, int n_kept, int Ct);
+// Frees every region buffer and forgets the spec (mk_session_set_test_sites; a NULL spec).
+void regions_detach(mk_session* s);
 
 }  // namespace mk

@@ -13,7 +13,7 @@ from ._lib import _ip, check, load
 from .glm import glm_binomial
 from .post import combine_median
 from .post import posterior_summary as _post_summary
-from .session import SamplerConfig, Session, combine
+from .session import SamplerConfig, Session, combine, map_grid
 
 PROBS200 = None
 
@@ -90,7 +90,7 @@ def r_sample_replace(n, size, seed):
 
 def meta_fit(y, x, weight, coords, q, index_part, coords_test=None, cfg=None, subset_base=0, device=0,
              cov_model="exponential", n_batch=100, batch_length=50, seed=20250114, x_test=None, diagnostics=False,
-             criteria=False, y_test=None, weights_test=1, maps=None, pairs=None):
+             criteria=False, y_test=None, weights_test=1, maps=None, pairs=None, regions=None):
     """All subsets of one shard on one GPU; returns the list `obj` of MK.R:108 for those subsets:
     [{'parameters': 200 x P, 'w.predict': 200 x (q n_test)}, ...]; with x_test (MK.R:87's x.test) each
     also holds 'p.predict' (200 x (q n_test)): the grid of p(y = 1) at the test sites.
@@ -105,27 +105,38 @@ def meta_fit(y, x, weight, coords, q, index_part, coords_test=None, cfg=None, su
     pairs (joint-exceedance thresholds, () for none; needs x_test and q >= 2): each also holds 'both.predict' and
     'diff.predict' (200 x C2: the grids of p_a p_b and p_a - p_b per site and outcome pair), 'pairs' (C2 x
     (6 + J) planes), 'pairs.names' (both_mean, both_sd, diff_mean, diff_sd, corr, a_gt_b, joint_1..J) and
-    'pairs.list' (the (a, b) in column order; Session.pairs)."""
+    'pairs.list' (the (a, b) in column order; Session.pairs).
+    regions (dict(offsets=..., weights=..., thresholds=...); needs x_test and cfg.predict_tile >= the number of
+    test sites): each also holds 'region.predict' (200 x C3: the grid of the regional prevalence per region and
+    outcome), 'regions' (C3 x (2 + J) planes), 'regions.names' (mean, sd, exc_1..J) and 'regions.singular'
+    (Session.regions; combine_regions combines the grids).  The joint draws need the exact tiled replay, so the
+    session is then created without test sites and kriges all of them after the run, in one tile."""
     p = np.asarray(x).shape[1]
     if cfg is None:
         beta0, bt = start_values(y, x, weight, q)
         cfg = default_config(q, p, beta0, bt, cov_model=cov_model, n_batch=n_batch, batch_length=batch_length,
                              seed=seed)
     subsets = [subset_data(y, x, weight, coords, q, idx) for idx in index_part]
-    with Session(subsets, cfg, coords_test=coords_test, subset_base=subset_base, device=device, x_test=x_test,
-                 criteria=criteria) as ses:
+    with Session(subsets, cfg, coords_test=None if regions is not None else coords_test, subset_base=subset_base,
+                 device=device, x_test=None if regions is not None else x_test, criteria=criteria) as ses:
+        if regions is not None:     # a tiled session: the chain states are recorded, the sites come after the run
+            ses.run(cfg.n_samples)
+            ses.set_test_sites(coords_test, x_test=x_test)
+            ses.set_regions(regions["offsets"], regions.get("weights"), regions.get("thresholds", ()))
         if y_test is not None:
             ses.set_validation(y_test, weights_test)
         if maps is not None:
             ses.set_maps(maps)
         if pairs is not None:
             ses.set_pairs(pairs)
-        ses.run(cfg.n_samples)
+        if regions is None:
+            ses.run(cfg.n_samples)
         out = ses.outputs(diagnostics=diagnostics)
         crit = ses.criteria() if criteria else None
         scores = ses.scores() if y_test is not None else None
         planes = ses.maps() if maps is not None else None
         pr = ses.pairs() if pairs is not None else None
+        rg = ses.regions() if regions is not None else None
     res = []
     for i in range(len(subsets)):
         d = {"parameters": out["parameters"][i]}
@@ -145,6 +156,9 @@ def meta_fit(y, x, weight, coords, q, index_part, coords_test=None, cfg=None, su
         if pr is not None:
             d["both.predict"], d["diff.predict"] = pr["both_predict"][i], pr["diff_predict"][i]
             d["pairs"], d["pairs.names"], d["pairs.list"] = pr["subsets"][i], list(pr["names"]), list(pr["pairs"])
+        if rg is not None:
+            d["region.predict"], d["regions"], d["regions.names"] = rg["region_predict"][i], rg["subsets"][i], list(rg["names"])
+            d["regions.singular"], d["regions.thresholds"] = rg["singular"][i], list(rg["thresholds"])
         res.append(d)
     return res
 
@@ -186,6 +200,17 @@ def combine_predictive(obj, device=0, method="mean"):
     if "p.predict" not in obj[0]:
         return None
     return combiner(method, device)([o["p.predict"] for o in obj])
+
+
+def combine_regions(obj, device=0, method="mean"):
+    """The subsets' region.predict grids combined as combine_predictive combines p.predict (200 x C3), and the
+    combined grid's planes by map_grid: {'region.predict', 'planes' (C3 x (2 + J)), 'names', 'thresholds'}; None
+    when the subsets were fitted without regions."""
+    if "region.predict" not in obj[0]:
+        return None
+    grid = combiner(method, device)([o["region.predict"] for o in obj])
+    m = map_grid(grid, obj[0].get("regions.thresholds", ()), device=device)
+    return {"region.predict": grid, "planes": m["planes"], "names": m["names"], "thresholds": m["thresholds"]}
 
 
 def convergence_report(diag, ess_min=100, rhat_max=1.05):

@@ -3,8 +3,8 @@ caller's layouts: one table of field -> shape serves Session.outputs and meta_fi
 import numpy as np
 
 from ._lib import (CRIT_NAMES, MAP_BASE_NAMES, N_CRIT, N_DIAG, N_LEVELS, N_MAP_BASE, N_PAIR_BASE, N_SCORE,
-                   PAIR_BASE_NAMES, SCORE_NAMES, Criteria, Diagnostics, MapSpec, Maps, Outputs, PairSpec, Pairs, Scores,
-                   Validation, dptr)
+                   PAIR_BASE_NAMES, REGION_BASE_NAMES, SCORE_NAMES, Criteria, Diagnostics, MapSpec, Maps, Outputs, PairSpec,
+                   Pairs, Regions, RegionSpec, Scores, Validation, dptr, iptr)
 
 # The array libmk fills for each mk_outputs field, row-major, in terms of: K subsets, P parameters,
 # C = q n_test kriging columns, L levels, n = n_samples, kept states, B amcmc batches, R = P + 1
@@ -239,4 +239,57 @@ class PairBuffers:
         for f in ("combined_both", "combined_diff"):
             if getattr(self, f) is not None:
                 out[f] = getattr(self, f).T.copy()
+        return out
+
+
+def region_spec(offsets, n_test, weights=None, thresholds=()):
+    """A region spec as libmk reads it: (offsets int32 [G + 1], weights float64 [n_test] or None, the
+    thresholds, the mk_region_spec pointing at them).  libmk checks all of it (include/mk.h "areal
+    prediction") and names the offending index."""
+    off = np.ascontiguousarray(np.asarray(offsets).reshape(-1), dtype=np.int32)
+    if off.size < 2:
+        raise ValueError("error: offsets must hold G + 1 >= 2 entries")
+    w = None
+    if weights is not None:
+        w = np.ascontiguousarray(np.asarray(weights, dtype=np.float64).reshape(-1))
+        if w.size != int(n_test):
+            raise ValueError(f"error: weights must hold one entry per test site ({int(n_test)}), not {w.size}")
+    u = np.ascontiguousarray(np.asarray(thresholds, dtype=np.float64).reshape(-1))
+    m = RegionSpec()
+    m.n_regions, m.offsets, m.weights = int(off.size - 1), iptr(off), dptr(w)
+    m.n_thresholds, m.thresholds = int(u.size), (dptr(u) if u.size else None)
+    return off, w, u, m
+
+
+def region_names(J):
+    return list(REGION_BASE_NAMES) + [f"exc_{j + 1}" for j in range(int(J))]
+
+
+class RegionBuffers:
+    """The arrays behind an mk_regions of K subsets of a q-outcome fit with G regions (C3 = G q region columns,
+    region-major) and J thresholds over `kept` states: `.c` points at them; unpack() gives {'names': mean, sd,
+    exc_1..J, 'thresholds', 'region_predict': per subset 200 x C3, 'subsets': per subset C3 x (2 + J),
+    'singular': per subset C3 (int32), 'timing_ms': covariance-and-factor, draws, grids-and-planes} and, with
+    samples, 'region_samples' (per subset C3 x kept)."""
+
+    def __init__(self, K, q, G, J, kept, samples=False):
+        self.K, self.q, self.G, self.J = int(K), int(q), int(G), int(J)
+        self.C3 = self.G * self.q
+        self.region_predict = np.zeros((self.K, self.C3, N_LEVELS))
+        self.planes = np.zeros((self.K, 2 + self.J, self.C3))
+        self.region_samples = np.zeros((self.K, int(kept), self.C3)) if samples else None
+        self.singular = np.zeros((self.K, self.C3), dtype=np.int32)
+        self.timing_ms = np.zeros(3)
+        self.c = Regions()
+        for f in ("region_predict", "planes", "region_samples", "timing_ms"):
+            setattr(self.c, f, dptr(getattr(self, f)))
+        self.c.singular = iptr(self.singular)
+
+    def unpack(self, thresholds=()):
+        out = {"names": region_names(self.J), "thresholds": [float(u) for u in thresholds],
+               "region_predict": [self.region_predict[i].T.copy() for i in range(self.K)],
+               "subsets": [self.planes[i].T.copy() for i in range(self.K)],
+               "singular": [self.singular[i].copy() for i in range(self.K)], "timing_ms": self.timing_ms.copy()}
+        if self.region_samples is not None:
+            out["region_samples"] = [self.region_samples[i].T.copy() for i in range(self.K)]
         return out

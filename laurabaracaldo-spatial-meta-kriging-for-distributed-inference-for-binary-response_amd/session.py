@@ -10,8 +10,8 @@ import numpy as np
 
 from . import _lib
 from ._lib import Config, Problem, check, dptr, iptr
-from .outbuf import (CriteriaBuffers, DiagnosticBuffers, MapBuffers, OutputBuffers, PairBuffers, ScoreBuffers, map_names,
-                     map_spec, pair_spec, validation_arrays)
+from .outbuf import (CriteriaBuffers, DiagnosticBuffers, MapBuffers, OutputBuffers, PairBuffers, RegionBuffers, ScoreBuffers,
+                     map_names, map_spec, pair_spec, region_spec, validation_arrays)
 
 COV_MODELS = {"exponential": _lib.MK_COV_EXPONENTIAL, "matern": _lib.MK_COV_MATERN}
 LINKS = {"logit": _lib.MK_LINK_LOGIT, "probit": _lib.MK_LINK_PROBIT}
@@ -24,6 +24,7 @@ KS_CRIT = 15      # the model-assessment launches (always timed; 0 launches unle
 KS_SCORE = 16     # the held-out scoring launches (always timed; 0 launches unless validation data were attached)
 KS_MAPS = 17      # the posterior-map launches (always timed; 0 launches unless maps were asked for)
 KS_PAIRS = 18     # the cross-outcome launches (always timed; 0 launches unless pairs were asked for)
+KS_REGIONS = 19   # the areal-prediction launches (always timed; 0 launches unless regions were attached)
 
 
 def _f64(a):
@@ -191,6 +192,7 @@ class Session:
         self._window = None     # kept states of the next outputs(), once set_kept_window narrowed them
         self._map_thresholds = None     # set_maps' thresholds while maps are attached
         self._pair_thresholds = None    # set_pairs' thresholds while pairs are attached
+        self._regions = None            # set_regions' (G, thresholds) while regions are attached
         # kriging fused into the kept iterations (mk_session_create's rule): a kept window then serves
         # criteria() alone, outputs() keeps every kept state
         self._fused = not (cfg.predict_tile > 0 and (self.n_test == 0 or cfg.predict_tile < self.n_test))
@@ -239,6 +241,7 @@ class Session:
         self.x_test = None
         self._map_thresholds = None     # the library detaches the maps with the sites
         self._pair_thresholds = None    # and the pairs
+        self._regions = None            # and the regions
         check(self._lib.mk_session_set_test_sites(self._h, self.n_test, dptr(self.coords_test)))
         if xt is not None:
             self.set_test_covars(xt, _flat=True)
@@ -386,6 +389,34 @@ class Session:
         pb = PairBuffers(self.S, self.q, self.n_test, u.size, grids=grids, planes=planes)
         check(self._lib.mk_session_pairs(self._h, ctypes.byref(pb.c)))
         return pb.unpack(u)
+
+    def set_regions(self, offsets, weights=None, thresholds=()):
+        """Attach regions to the current test sites (mk_session_set_regions): offsets[0..G] cuts the sites, in
+        their order, into G contiguous runs of at most 128; weights (one per site, default equal) make the
+        regional prevalence r = sum_i omega_i p_i of joint kriging draws of the region's sites; thresholds (at
+        most 8) give the posterior probability that r > u.  Needs a session created with predict_tile > 0 whose
+        tile holds every test site, x_test and recorded samples.  regions() then gives the outputs of the
+        replay that makes the grids (outputs(), tile_grids()).  offsets=None detaches; so does set_test_sites."""
+        self._regions = None
+        if offsets is None:
+            check(self._lib.mk_session_set_regions(self._h, None))
+            return
+        off, _w, u, m = region_spec(offsets, self.n_test, weights, thresholds)
+        check(self._lib.mk_session_set_regions(self._h, ctypes.byref(m)))
+        self._regions = (int(off.size - 1), u)
+
+    def regions(self, samples=False):
+        """The areal prediction per subset after a replay (mk_session_regions; the definitions are in
+        include/mk.h): {'names': mean, sd, exc_1..J, 'thresholds', 'region_predict': per subset 200 x C3,
+        'subsets': per subset C3 x (2 + J), 'singular': per subset C3 counts of kept states whose factor was
+        flagged, 'timing_ms'}, C3 = G q region columns (region-major); samples=True adds 'region_samples' (per
+        subset C3 x kept).  The tile must have been replayed over the current kept window since set_regions
+        (MkError otherwise)."""
+        G, u = self._regions if self._regions is not None else (0, np.zeros(0))
+        kept = self.cfg.kept if self._window is None else self._window
+        rb = RegionBuffers(self.S, self.q, G, u.size, kept, samples=samples)
+        check(self._lib.mk_session_regions(self._h, ctypes.byref(rb.c)))
+        return rb.unpack(u)
 
     def set_lookahead(self, mode):
         """Launch schedule before the first run: True / 1 lookahead (the next iteration's phi

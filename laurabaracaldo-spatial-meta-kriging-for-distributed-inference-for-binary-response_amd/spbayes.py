@@ -271,6 +271,59 @@ def spPairs(sp_obj, pred_coords, pred_covars, thresholds=(), start=1, end=None):
     return res
 
 
+def spRegions(sp_obj, pred_coords, pred_covars, region, weights=None, thresholds=(), start=1, end=None, samples=False):
+    """Areal prediction of an spMvGLM fit, on the device: `region` is an integer label per prediction site; per
+    region (in ascending label order, "region.labels") and outcome a -- region column g q + a -- the prevalence
+    r = sum_i omega_i p_i,a over the region's sites (omega: `weights` normalised within the region, default
+    equal) drawn jointly across the sites per kept state.  Returns "region.predict" (200 x C3: its 200-level
+    grid), "region.mean", "region.sd" (each C3), "region.exceed" (C3 x J: the posterior probability that r
+    exceeds each threshold), "region.singular" (C3: kept states whose joint covariance factor was flagged),
+    "region.labels", "thresholds" and, with samples=True, "region.samples" (C3 x kept); over iterations
+    start..end (1-based, inclusive), kriged from the recorded chain in one replay.  A region holds at most 128
+    sites.  The sites are sorted by label (stable) for the replay.  The definitions are in include/mk.h."""
+    ses = sp_obj.get("_session")
+    if ses is None:
+        raise ValueError("error: the spMvGLM fit was closed; spRegions needs its recorded chain states")
+    n_samples = sp_obj["_n_samples"]
+    end = n_samples if end is None else int(end)
+    start = int(start)
+    if not (1 <= start <= end <= n_samples):
+        raise ValueError("error: invalid start/end")
+    ct = np.asarray(pred_coords, float).reshape(-1, 2)
+    n = ct.shape[0]
+    xt = np.asarray(pred_covars, float)
+    if xt.ndim != 2 or xt.shape[0] != ses.q * n:
+        raise ValueError("error: pred.covars must have one row per prediction site and outcome (q * n rows)")
+    lab = np.asarray(region).reshape(-1)
+    if lab.shape[0] != n or not np.issubdtype(lab.dtype, np.integer):
+        raise ValueError("error: region must hold one integer label per prediction site")
+    order = np.argsort(lab, kind="stable")
+    labels, counts = np.unique(lab, return_counts=True)
+    offsets = np.concatenate([[0], np.cumsum(counts)])
+    rows = (order[:, None] * ses.q + np.arange(ses.q)[None, :]).reshape(-1)
+    w = None
+    if weights is not None:
+        w = np.asarray(weights, float).reshape(-1)
+        if w.shape[0] != n:
+            raise ValueError("error: weights must hold one entry per prediction site")
+        w = w[order]
+    ses.set_test_sites(ct[order], x_test=xt[rows])
+    ses.set_kept_window(start, end)
+    ses.set_regions(offsets, w, thresholds)
+    try:
+        ses.outputs(quantiles=False, w_predict_sum=True)      # the one replay of the window
+        m = ses.regions(samples=samples)
+    finally:
+        ses.set_regions(None)
+    pl = m["subsets"][0]
+    res = {"region.predict": m["region_predict"][0], "region.mean": pl[:, 0].copy(), "region.sd": pl[:, 1].copy(),
+           "region.exceed": pl[:, 2:].copy(), "region.singular": m["singular"][0], "region.labels": labels.tolist(),
+           "thresholds": m["thresholds"]}
+    if samples:
+        res["region.samples"] = m["region_samples"][0]
+    return res
+
+
 def spPredict(sp_obj, pred_coords, pred_covars=None, start=1, end=None, thin=1, diagnostics=False):
     """p.w.predictive.samples ((q n_test) x kept) for kept iterations start..end (1-based,
     inclusive; every thin-th), kriged from the chain states spMvGLM recorded (no refit).
