@@ -203,7 +203,8 @@ int mk_session_tile_grids_wp(mk_session* s, int32_t t0, double* out_w, double* o
  * attached; 17 the posterior-map launches k_map_cols -- launches and ms, always timed, 0 launches unless
  * maps were asked for; 18 the cross-outcome launches k_quantiles_pair / k_pair_cols -- launches (one per
  * kernel) and ms, always timed, 0 launches unless pairs were asked for; 19 the areal-prediction launches
- * k_region_cov / k_region_draw per kept state and k_quantiles / k_map_cols per replay -- launches (one per
+ * k_region_cov / k_region_draw per kept state and k_quantiles / k_map_cols per replay (on the interpolated
+ * route the node covariances, the check and two launches per chunk of kept states) -- launches (one per
  * kernel) and ms, always timed, 0 launches unless regions were attached).  Flops are algorithmic, not executed: GEMM tiles 2 m n k, the diagonal tile's
  * update as a SYRK, solves and inverse products over their triangles.  mk_session_profile(s, enable)
  * before mk_session_run: enable 0 = off, 1 = every kind, otherwise a mask with bit (1 + kind) per kind
@@ -583,13 +584,30 @@ int mk_meta_fit_pairs(const mk_problem* prob, const mk_config* cfg, const int32_
  *   singular        int32 [C3]: the kept states of the window whose factor for (region g, outcome a) was
  *                   flagged, at column g q + a
  * The regions need a session created with predict_tile > 0 whose tile holds every test site: the joint
- * covariance is formed from X = W P^T, which only the exact tiled replay has in HBM.  While regions are
- * attached the phi-interpolated replay is not used, so the tile's other outputs (grids, draws, maps, pairs,
- * scores) are the exact replay's: they agree with the interpolated ones to the documented 1e-8, not bit for
- * bit.  The fused (in-chain) route, the node call, regions above MK_REGION_MAXM sites or across tiles, and a
- * thinned replay are not covered. */
+ * covariance is formed from X = W P^T, which the tiled replay has in HBM.  Two routes serve them.
+ * MK_REGIONS_EXACT (the default): the exact tiled replay forms and factors S_h at every kept state whose phi_h
+ * changed; while regions are attached on this route the phi-interpolated replay is not used, so the tile's
+ * other outputs (grids, draws, maps, pairs, scores) are the exact replay's: they agree with the interpolated
+ * ones to the documented 1e-8, not bit for bit.
+ * MK_REGIONS_INTERP (mk_session_set_regions_route): the tile replay interpolates wherever it would without
+ * regions (exponential models, MK_KRIG_CHEB's auto rule or its forcing, the checks passed).  S_h depends on
+ * phi_h alone and is analytic in it like s(t; phi): its lower triangle is formed exactly at the replay's
+ * Chebyshev nodes and check slots (the node-count rule's d_max then also covers the largest distance inside a
+ * region), interpolated with the same barycentric weights (a node hit returns the node's value) at every
+ * distinct phi_h of the window, and factored with the same pivot rule.  The interpolant's largest |difference|
+ * from the exact S at the check slots joins the replay's own check: above MK_KRIG_CHEB_TOL the whole tile
+ * runs exactly, as does a tile whose node, means or factor buffers do not fit in HBM.  The means are the
+ * interpolated replay's m_k,h(t); the normals, the summation orders, the A mix, pred_prob, the weighted sum
+ * and the flagged-factor count are those above.  The draws agree with the exact route's to about
+ * cond(S_h) x the check, and the tile's other outputs are, bit for bit, those of the interpolated replay
+ * without regions.  The kept window is processed in chunks of consecutive states (as many as a factor scratch
+ * of 1 GiB holds; MK_REGIONS_CHUNK overrides); the results do not depend on the chunk length.
+ * The fused (in-chain) route, the node call, regions above MK_REGION_MAXM sites or across tiles, a Matern
+ * interpolation and a thinned replay are not covered. */
 #define MK_REGION_MAXM 128          /* sites per region at most */
 #define MK_REGION_PIVOT_TOL 1e-12   /* a pivot of S_h that is not above this zeroes its column */
+#define MK_REGIONS_EXACT 0          /* routes of the areal prediction: the exact tiled replay */
+#define MK_REGIONS_INTERP 1         /* the phi-interpolated replay wherever it would run without regions */
 typedef struct mk_region_spec {
   int32_t n_regions;           /* G */
   const int32_t* offsets;      /* [G + 1] */
@@ -602,8 +620,10 @@ typedef struct mk_regions {           /* caller-allocated, any pointer may be NU
   double* planes;              /* [n_subsets] x (C3 x (2 + J)) */
   double* region_samples;      /* [n_subsets] x (C3 x kept) */
   int32_t* singular;           /* [n_subsets] x C3 */
-  double* timing_ms;           /* [3]: the region launches' time since the attach -- covariance and factor,
-                                  draws, grids and planes (HIP events; kernel kind 19 holds their sum) */
+  double* timing_ms;           /* [3]: the region launches' time since the attach -- covariance and factor
+                                  (on the interpolated route the node covariances, the check and the
+                                  interpolate-and-factor launches), draws, grids and planes (HIP events;
+                                  kernel kind 19 holds their sum) */
 } mk_regions;
 /* Attach a region spec to the session's current test sites (NULL detaches and frees).  Everything is checked
  * on the host before any device is touched, each failure MK_E_ARG naming the offending index: bad offsets, a
@@ -616,6 +636,15 @@ typedef struct mk_regions {           /* caller-allocated, any pointer may be NU
  * mk_session_set_test_sites detaches.  Nothing is launched or allocated for the regions unless they were
  * attached. */
 int mk_session_set_regions(mk_session* s, const mk_region_spec* spec);
+/* The route of the attached regions (MK_REGIONS_EXACT or MK_REGIONS_INTERP; anything else, or no attached
+ * spec, is MK_E_ARG).  Called after mk_session_set_regions: attaching or detaching a spec resets the route to
+ * MK_REGIONS_EXACT.  Nothing is allocated here: the interpolated route takes its buffers inside a tile replay
+ * and frees them before it returns. */
+int mk_session_set_regions_route(mk_session* s, int32_t route);
+/* asked: the route set; ran: the route the last tile replay took (MK_REGIONS_EXACT before any); check: that
+ * replay's largest |interpolant - exact| over the entries of S_h at the check slots, 0 when the exact route
+ * ran.  Any pointer may be NULL.  MK_E_ARG without an attached spec. */
+int mk_session_regions_route(mk_session* s, int32_t* asked, int32_t* ran, double* check);
 /* After all iterations: copies the buffers out.  MK_E_ARG if the tile has not been replayed over the current
  * kept window since the regions were attached. */
 int mk_session_regions(mk_session* s, mk_regions* out);

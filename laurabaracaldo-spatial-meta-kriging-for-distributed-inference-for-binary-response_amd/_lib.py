@@ -36,6 +36,8 @@ N_PAIR_BASE = 6        # MK_N_PAIR_BASE: the pair planes before joint_1..J, in P
 PAIR_BASE_NAMES = ["both_mean", "both_sd", "diff_mean", "diff_sd", "corr", "a_gt_b"]
 REGION_MAXM = 128      # MK_REGION_MAXM: sites per region at most
 REGION_BASE_NAMES = ["mean", "sd"]     # the region planes before exc_1..J
+REGIONS_EXACT, REGIONS_INTERP = 0, 1    # MK_REGIONS_EXACT, MK_REGIONS_INTERP: the routes of the areal prediction
+REGION_ROUTE_NAMES = ["exact", "interpolated"]
 
 _dp = ctypes.POINTER(ctypes.c_double)
 _ip = ctypes.POINTER(ctypes.c_int32)
@@ -150,6 +152,8 @@ EXPORTS = {
     "mk_session_pairs": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(Pairs)]),
     "mk_session_set_regions": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(RegionSpec)]),
     "mk_session_regions": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(Regions)]),
+    "mk_session_set_regions_route": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32]),
+    "mk_session_regions_route": (ctypes.c_int, [ctypes.c_void_p, _ip, _ip, _dp]),
     "mk_session_set_maps": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(MapSpec)]),
     "mk_session_maps": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(Maps)]),
     "mk_map_grid": (ctypes.c_int, [_dp, ctypes.c_int32, ctypes.c_int64, _dp, ctypes.c_int32, _dp, ctypes.c_int32]),

@@ -123,9 +123,9 @@ __global__ void k_cheb_check(Model md, ChebK c, unsigned long long* err);
 __global__ void k_kt_snap(Model md, double* zs, double* phis, double* As);
 __global__ void k_pred_tab_draw(Model md, ChebK c, const double* g, const double* coords, const double* phis,
                                 const double* As, int iter, int kidx);
-template <int Q>
+template <int Q, bool MEANS>
 __global__ void k_pred_cheb_draw(Model md, ChebK c, const double* Gt, const double* phit, const double* coords,
-                                 const double* kA, int k_lo, int nkp);
+                                 const double* kA, int k_lo, int nkp, double* means);
 // mk_criteria.hip
 __global__ void k_crit_accum(Model md, Crit c, int kidx);
 __global__ void k_crit_replay(Model md, Crit c, int first, int n, int thin);

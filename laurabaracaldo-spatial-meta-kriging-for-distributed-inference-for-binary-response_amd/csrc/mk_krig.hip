@@ -262,15 +262,13 @@ static int tile_outputs(mk_session* s, int t0, double* dq, double* dqp, mk_outpu
 // exact values at nchk check points (the range's ends, then interior points) bound the interpolant's
 // error before any draw uses it.
 
-// The φ-interpolated paths return 0 when done, this when the exact path must run instead (not
-// applicable, scratch memory short, a check failed), and an MK_E_* code (< 0) on an error.
-constexpr int MK_CHEB_EXACT = 1;
-
 // Nodes of [lo, hi] for each (subset, outcome) pair i = s q + h: nc[i], the slots' phi (nodes, then nchk
-// check points) and the barycentric weights; d_max is the subset's.  Returns the slot count E (the
-// largest nc + nchk).
+// check points) and the barycentric weights; d_max is the subset's, and at least dmax_regions (the largest
+// distance inside a region while regions are on the interpolated route, else 0: S_h holds the correlations
+// between a region's sites).  Returns the slot count E (the largest nc + nchk).
 static int cheb_plan(mk_session* s, const std::vector<double>& lo, const std::vector<double>& hi, int force_n, int nchk,
-                     std::vector<int>& nc, std::vector<std::vector<double>>& sphi, std::vector<double>& wts) {
+                     std::vector<int>& nc, std::vector<std::vector<double>>& sphi, std::vector<double>& wts,
+                     double dmax_regions = 0.0) {
   const int S = s->S * s->q;
   nc.assign(S, 0);
   sphi.assign(S, {});
@@ -278,7 +276,7 @@ static int cheb_plan(mk_session* s, const std::vector<double>& lo, const std::ve
   int E = 0;
   for (int i = 0; i < S; ++i) {
     const double* bb = s->bbox.data() + 4 * (i / s->q);
-    const double dmax = std::fmax(s->span_pt_h[i / s->q], std::hypot(bb[1] - bb[0], bb[3] - bb[2]));
+    const double dmax = std::fmax(std::fmax(s->span_pt_h[i / s->q], std::hypot(bb[1] - bb[0], bb[3] - bb[2])), dmax_regions);
     const int n = force_n > 1 ? std::min(force_n, MK_CHEB_MAX)
                               : std::max(10, std::min(MK_CHEB_MAX, 6 + (int)std::ceil((hi[i] - lo[i]) * dmax)));
     nc[i] = n;
@@ -305,8 +303,12 @@ static int cheb_plan(mk_session* s, const std::vector<double>& lo, const std::ve
 // its first node, so the record stays a valid theta).  The factor slots, cur and W serve as scratch:
 // callers are the tiled replay (the chain is finished) and session set-up (before the initial
 // factorisation).  The host stays at most four slots ahead of the device.
+// ri (regions on the interpolated route, else NULL): every slot's X also gives the regions' S (regions_node),
+// and the interpolant of S is checked like that of s (regions_check; its own largest difference into
+// *emax_regions, and folded into *emax).
 static int cheb_eval(mk_session* s, Model mt, const std::vector<int>& nc, const std::vector<std::vector<double>>& sphi,
-                     const std::vector<double>& wts, int E, int nchk, DevBufs& scratch, ChebK* ck, double* emax) {
+                     const std::vector<double>& wts, int E, int nchk, DevBufs& scratch, ChebK* ck, double* emax,
+                     RegionInterp* ri = nullptr, double* emax_regions = nullptr) {
   Model& md = s->md;
   const int S = s->S, q = s->q, SQ = S * q, nth = md.n_theta, T_pad = md.n_test_pad;
   hipStream_t st = s->stream;
@@ -371,6 +373,10 @@ static int cheb_eval(mk_session* s, Model mt, const std::vector<int>& nc, const 
     gp.d_pcount = C;
     launch_pred_refresh(s, gp);
     HIPCHK(hipGetLastError());
+    if (ri) {
+      const int rc = regions_node(s, gp, *ri, e);
+      if (rc) return rc;
+    }
     if (e % 4 == 3) HIPCHK(hipStreamSynchronize(st));   // four slots are ~0.6 s of GEMMs at configs[4]
   }
   ck->Sn = d_Sn;
@@ -384,6 +390,11 @@ static int cheb_eval(mk_session* s, Model mt, const std::vector<int>& nc, const 
   HIPCHK(hipMemcpyAsync(&eb, d_err, 8, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
   std::memcpy(emax, &eb, 8);
+  if (ri) {
+    const int rc = regions_check(s, *ri, *ck, emax_regions);
+    if (rc) return rc;
+    if (!(*emax_regions <= *emax)) *emax = *emax_regions;   // the kernel turned a NaN into +inf
+  }
   return 0;
 }
 
@@ -481,7 +492,10 @@ static int predict_tile_cheb(mk_session* s, int t0, double* dq, mk_outputs* o, d
   Model& md = s->md;
   const int force_n = cheb_mode();
   if (force_n == 0 || md.cov_model != MK_COV_EXPONENTIAL) return MK_CHEB_EXACT;
-  if (s->regions.on) return MK_CHEB_EXACT;   // the joint covariance of a region needs X, which only the exact replay forms
+  // the joint covariance of a region needs X: the exact replay forms it at every state, this one at its nodes,
+  // which serves the regions only on the route that asks for it
+  const bool rint = s->regions.on && s->regions.route == MK_REGIONS_INTERP;
+  if (s->regions.on && !rint) return MK_CHEB_EXACT;
   const int S = s->S, q = s->q, SQ = S * q, nth = md.n_theta, n_pad = md.n_pad;
   const int k_lo = s->win_lo, n_kept = s->win_n < 0 ? md.n_kept : s->win_n;
   if (n_kept < 1 || (int)s->span_pt_h.size() != S) return MK_CHEB_EXACT;
@@ -534,7 +548,7 @@ static int predict_tile_cheb(mk_session* s, int t0, double* dq, mk_outputs* o, d
   std::vector<int> nc;
   std::vector<std::vector<double>> sphi;
   std::vector<double> wts;
-  const int E = cheb_plan(s, lo, hi, force_n, MK_CHEB_CHECKS, nc, sphi, wts);
+  const int E = cheb_plan(s, lo, hi, force_n, MK_CHEB_CHECKS, nc, sphi, wts, rint ? s->regions.dmax : 0.0);
   long evals = 0;
   for (int i = 0; i < SQ; ++i) evals += nc[i] + MK_CHEB_CHECKS;
   // auto: only where it saves exact evaluations, summed over the pairs -- the exact replay refreshes a
@@ -587,9 +601,14 @@ static int predict_tile_cheb(mk_session* s, int t0, double* dq, mk_outputs* o, d
   mt.t_off = t0;
   mt.ntt = (Tc + MK_NB - 1) / MK_NB;
   DevBufs scratch;
+  RegionInterp ri;   // the regions' node, means and factor-chunk buffers: this replay's, and only on their route
+  if (rint) {
+    const int rb = regions_interp_begin(s, ri, t0, Tc, n_kept, E);
+    if (rb) return rb;   // HBM short (MK_CHEB_EXACT: the tile runs exactly, as without the route) or an error
+  }
   ChebK ck;
-  double emax = 0.0;
-  const int rc = cheb_eval(s, mt, nc, sphi, wts, E, MK_CHEB_CHECKS, scratch, &ck, &emax);
+  double emax = 0.0, emax_regions = 0.0;
+  const int rc = cheb_eval(s, mt, nc, sphi, wts, E, MK_CHEB_CHECKS, scratch, &ck, &emax, rint ? &ri : nullptr, &emax_regions);
   if (rc) return rc;
   if (!(emax <= cheb_tol())) {
     Stat& f = s->prof.stats[KS_KRIG_FALLBACK];
@@ -598,11 +617,20 @@ static int predict_tile_cheb(mk_session* s, int t0, double* dq, mk_outputs* o, d
     return MK_CHEB_EXACT;
   }
   // 5. the draws
-  void (*k_pred_cheb_draw_q)(Model, ChebK, const double*, const double*, const double*, const double*, int, int) =
-      q == 1 ? k_pred_cheb_draw<1> : q == 2 ? k_pred_cheb_draw<2> : q == 3 ? k_pred_cheb_draw<3> : k_pred_cheb_draw<4>;
+  void (*k_pred_cheb_draw_q)(Model, ChebK, const double*, const double*, const double*, const double*, int, int, double*) =
+      rint ? (q == 1 ? k_pred_cheb_draw<1, true> : q == 2 ? k_pred_cheb_draw<2, true> : q == 3 ? k_pred_cheb_draw<3, true>
+                                                                                               : k_pred_cheb_draw<4, true>)
+           : (q == 1 ? k_pred_cheb_draw<1, false> : q == 2 ? k_pred_cheb_draw<2, false> : q == 3 ? k_pred_cheb_draw<3, false>
+                                                                                                  : k_pred_cheb_draw<4, false>);
   MK_LAUNCH(k_pred_cheb_draw_q, dim3(S * ((Tc + 255) / 256)), dim3(256), 0, st, mt, ck, s->cg.G, s->cg.phit, md.coords,
-            md.kA, k_lo, nkp);
+            md.kA, k_lo, nkp, ri.means);
   HIPCHK(hipGetLastError());
+  if (rint) {   // the factors of every chunk's phi runs and the regional draws, from the nodes' S and the means
+    const int rr = regions_interp_draws(s, ri, mt, ck, n_kept);
+    if (rr) return rr;
+    s->regions.ran = MK_REGIONS_INTERP;
+    s->regions.check = emax_regions;
+  }
   Stat& c = s->prof.stats[KS_KRIG_CHEB];
   c.launches += 1;
   c.flops += (double)evals;
@@ -626,6 +654,10 @@ int mk::predict_tile(mk_session* s, int t0, double* dq, mk_outputs* o, double* d
   // the flag of a lookahead candidate that no iteration will decide on is not a kept state's
   // (tile_outputs reads the flags after the replay)
   HIPCHK(hipMemsetAsync(s->md.info, 0, (size_t)s->S * s->q * sizeof(int), s->stream));
+  if (s->regions.on) {   // until the interpolated route has served them
+    s->regions.ran = MK_REGIONS_EXACT;
+    s->regions.check = 0.0;
+  }
   const int rc_cheb = predict_tile_cheb(s, t0, dq, o, dqp);
   if (rc_cheb != MK_CHEB_EXACT) return rc_cheb;
   Model& md = s->md;

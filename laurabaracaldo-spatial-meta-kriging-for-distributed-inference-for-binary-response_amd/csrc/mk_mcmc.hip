@@ -2005,11 +2005,14 @@ __global__ __launch_bounds__(256) void k_cheb_check(Model md, ChebK c, unsigned 
 // padded to nkp (a multiple of 8), and with the coordinates and A they are read through scalar loads
 // (uniform addresses).  Every loop over Q and the 8 states is unrolled, so p, a, sd and v are indexed
 // at compile time only (registers, no scratch).  Q = 1 is the arithmetic of k_pred_draw_runs' draw.
-template <int Q>
+// MEANS (areal prediction on the interpolated route): the per-outcome means a[h][b] also go to means
+// ([S][n_kept][n_test Q], w_pred's layout) for k_region_draw<true>; the false instantiations never touch it.
+template <int Q, bool MEANS>
 __global__ __launch_bounds__(256) void k_pred_cheb_draw(Model md, ChebK c, const double* __restrict__ Gt,
                                                         const double* __restrict__ phit,
                                                         const double* __restrict__ coords,
-                                                        const double* __restrict__ kA, int k_lo, int nkp) {
+                                                        const double* __restrict__ kA, int k_lo, int nkp,
+                                                        double* __restrict__ means) {
   const int nb = (md.n_test + 255) / 256;
   const int s = blockIdx.x / nb;
   const int t0 = (blockIdx.x % nb) * 256 + threadIdx.x;
@@ -2070,17 +2073,30 @@ __global__ __launch_bounds__(256) void k_pred_cheb_draw(Model md, ChebK c, const
         for (int h = 0; h < Q; ++h) o += v[h] * A[r + h * Q];
         if (act) out[r] = o;
       }
+      if (MEANS && act) {
+        double* mu = means + ((long)s * n + j0 + b) * Q * md.n_test + (long)t * Q;
+#pragma unroll
+        for (int h = 0; h < Q; ++h) mu[h] = a[h][b];
+      }
     }
   }
 }
-template __global__ void k_pred_cheb_draw<1>(Model, ChebK, const double*, const double*, const double*, const double*,
-                                             int, int);
-template __global__ void k_pred_cheb_draw<2>(Model, ChebK, const double*, const double*, const double*, const double*,
-                                             int, int);
-template __global__ void k_pred_cheb_draw<3>(Model, ChebK, const double*, const double*, const double*, const double*,
-                                             int, int);
-template __global__ void k_pred_cheb_draw<4>(Model, ChebK, const double*, const double*, const double*, const double*,
-                                             int, int);
+template __global__ void k_pred_cheb_draw<1, false>(Model, ChebK, const double*, const double*, const double*,
+                                                    const double*, int, int, double*);
+template __global__ void k_pred_cheb_draw<2, false>(Model, ChebK, const double*, const double*, const double*,
+                                                    const double*, int, int, double*);
+template __global__ void k_pred_cheb_draw<3, false>(Model, ChebK, const double*, const double*, const double*,
+                                                    const double*, int, int, double*);
+template __global__ void k_pred_cheb_draw<4, false>(Model, ChebK, const double*, const double*, const double*,
+                                                    const double*, int, int, double*);
+template __global__ void k_pred_cheb_draw<1, true>(Model, ChebK, const double*, const double*, const double*,
+                                                    const double*, int, int, double*);
+template __global__ void k_pred_cheb_draw<2, true>(Model, ChebK, const double*, const double*, const double*,
+                                                    const double*, int, int, double*);
+template __global__ void k_pred_cheb_draw<3, true>(Model, ChebK, const double*, const double*, const double*,
+                                                    const double*, int, int, double*);
+template __global__ void k_pred_cheb_draw<4, true>(Model, ChebK, const double*, const double*, const double*,
+                                                    const double*, int, int, double*);
 
 // Fused kriging from the session's phi tables (mk_api.hip krig_tables; q = 1): what a kept iteration's
 // draws read, captured after its sweep (z, phi, A), so they can run on a side stream while the next

@@ -32,6 +32,7 @@
 #include "mk_internal.hpp"
 #include "mk_tilefill.hpp"
 #include "mk_regionspec.hpp"
+#include "mk_regionchunk.hpp"
 
 namespace mk {
 int set_err(int code, const std::string& msg);   // mk_api.hip: sets mk_last_error(), returns code
@@ -109,10 +110,16 @@ enum { KS_CHOL_UPDATE = 0, KS_CHOL_DIAG, KS_CHOL_TRSM, KS_SWEEP, KS_LAUUM, KS_IT
 // what mk_session_pairs is asked for of a fused one; launches counts kernels), bracketed by events whether or
 // not the profiler is on; none are made unless pairs were asked for.
 // KS_REGIONS: the areal-prediction launches (k_region_cov per kept state whose dirty list may hold a pair,
-// k_region_draw per kept state, then k_quantiles and k_map_cols per tile replay; launches counts kernels),
-// bracketed by events whether or not the profiler is on; none are made unless regions were attached.
+// k_region_draw per kept state, then k_quantiles and k_map_cols per tile replay; on the interpolated route
+// k_region_cov_node per node and check slot, k_region_check, and k_region_interp_factor and k_region_draw per
+// chunk of kept states in their place; launches counts kernels), bracketed by events whether or not the
+// profiler is on; none are made unless regions were attached.
 // KS_SWEEP_FALLBACK: launches = (subset, iteration) sweeps k_sweep_mg refused admission and its
 // k_sweep fallback ran (counted on the device, read at the end of every mk_session_run; no timing).
+
+// What a phi-interpolated path returns when the exact path must run instead (not applicable, scratch memory
+// short, a check failed); 0 when done, an MK_E_* code (< 0) on an error.
+constexpr int MK_CHEB_EXACT = 1;
 
 struct Stat {
   long launches = 0;
@@ -320,6 +327,25 @@ struct Regions {
   struct Ev { int part; hipEvent_t a, b; long launches; };
   std::vector<Ev> pending;    // events of the launches inside the replay loop, priced by tile_regions
   double ms[3] = {0.0, 0.0, 0.0};   // since the attach: covariance and factor | draws | grids and planes
+  int route = MK_REGIONS_EXACT;     // asked for (mk_session_set_regions_route)
+  int ran = MK_REGIONS_EXACT;       // the route of the last tile replay
+  double check = 0.0;               // that replay's largest |interpolant - exact| over the entries of S (0: exact route)
+  double dmax = 0.0;                // the largest site-to-site distance inside a region (the node-count rule)
+};
+
+// The interpolated route's scratch of one tile replay (regions_interp_begin takes it, the replay's return
+// frees it): nothing of it exists while the exact route runs.
+struct RegionInterp {
+  DevBufs bufs;
+  double* Sn = nullptr;       // [E][S q][fsz]: the lower triangle of S at every node and check slot, packed like the factors
+  double* means = nullptr;    // [S][n_kept][q n_test]: k_pred_cheb_draw's per-outcome means
+  double* Lc = nullptr;       // [S q][B][fsz]: the factors of one chunk's phi runs
+  int* flagc = nullptr;       // [S q][B][G]
+  int* slot = nullptr;        // [n_kept][S q]
+  RegionJob* jobs = nullptr;
+  unsigned long long* err = nullptr;
+  RegionChunkPlan plan;
+  int E = 0;
 };
 
 }  // namespace mk
@@ -603,6 +629,18 @@ void pairs_detach(mk_session* s);
 // of the pairs on g's dirty list, then that state's regional draws of every subset.
 int regions_begin(mk_session* s, int t0, int Tc, int n_kept);
 int regions_state(mk_session* s, Group& g, const Model& mt, int iter, int j, int n_kept);
+// The phi-interpolated replay's hooks while regions are attached on the interpolated route.  Each returns 0,
+// an error (< 0) or, regions_interp_begin alone, MK_CHEB_EXACT.
+// regions_interp_begin: regions_begin, then the node, means and factor-chunk buffers of a replay with E slots and
+// the chunk plan from the window's phi (s->cg.phi_h); MK_CHEB_EXACT when HBM is short: the tile runs exactly.
+// regions_node: after launch_pred_refresh of slot e -- S of the pairs on gp's list into the node buffer.
+// regions_check: the interpolant of S against the exact S at the check slots (ck: cheb_eval's nodes), the
+// largest |difference| into *emax; waits for the stream.
+// regions_interp_draws: per chunk the factors of its phi runs, then the regional draws of its states.
+int regions_interp_begin(mk_session* s, RegionInterp& ri, int t0, int Tc, int n_kept, int E);
+int regions_node(mk_session* s, const Group& gp, RegionInterp& ri, int e);
+int regions_check(mk_session* s, RegionInterp& ri, const ChebK& ck, double* emax);
+int regions_interp_draws(mk_session* s, RegionInterp& ri, const Model& mt, const ChebK& ck, int n_kept);
 // The regions' share of a tile replay: the grids and planes of the regional draws the replay left, timed as
 // KS_REGIONS.  Returns after the stream is idle.
 int tile_regions(mk_session* s, int t0, int n_kept, int Ct);

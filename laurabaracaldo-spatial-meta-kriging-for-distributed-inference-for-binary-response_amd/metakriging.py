@@ -106,11 +106,12 @@ def meta_fit(y, x, weight, coords, q, index_part, coords_test=None, cfg=None, su
     'diff.predict' (200 x C2: the grids of p_a p_b and p_a - p_b per site and outcome pair), 'pairs' (C2 x
     (6 + J) planes), 'pairs.names' (both_mean, both_sd, diff_mean, diff_sd, corr, a_gt_b, joint_1..J) and
     'pairs.list' (the (a, b) in column order; Session.pairs).
-    regions (dict(offsets=..., weights=..., thresholds=...); needs x_test and cfg.predict_tile >= the number of
+    regions (dict(offsets=..., weights=..., thresholds=..., interpolate=...); needs x_test and cfg.predict_tile >= the number of
     test sites): each also holds 'region.predict' (200 x C3: the grid of the regional prevalence per region and
     outcome), 'regions' (C3 x (2 + J) planes), 'regions.names' (mean, sd, exc_1..J) and 'regions.singular'
-    (Session.regions; combine_regions combines the grids).  The joint draws need the exact tiled replay, so the
-    session is then created without test sites and kriges all of them after the run, in one tile."""
+    (Session.regions; combine_regions combines the grids).  The joint draws need the tiled
+    replay (the exact one, or with interpolate=True the phi-interpolated one where it applies), so the session
+    is then created without test sites and kriges all of them after the run, in one tile."""
     p = np.asarray(x).shape[1]
     if cfg is None:
         beta0, bt = start_values(y, x, weight, q)
@@ -122,7 +123,8 @@ def meta_fit(y, x, weight, coords, q, index_part, coords_test=None, cfg=None, su
         if regions is not None:     # a tiled session: the chain states are recorded, the sites come after the run
             ses.run(cfg.n_samples)
             ses.set_test_sites(coords_test, x_test=x_test)
-            ses.set_regions(regions["offsets"], regions.get("weights"), regions.get("thresholds", ()))
+            ses.set_regions(regions["offsets"], regions.get("weights"), regions.get("thresholds", ()),
+                            interpolate=regions.get("interpolate", False))
         if y_test is not None:
             ses.set_validation(y_test, weights_test)
         if maps is not None:

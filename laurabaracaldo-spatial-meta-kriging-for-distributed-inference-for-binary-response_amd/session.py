@@ -390,13 +390,18 @@ class Session:
         check(self._lib.mk_session_pairs(self._h, ctypes.byref(pb.c)))
         return pb.unpack(u)
 
-    def set_regions(self, offsets, weights=None, thresholds=()):
+    def set_regions(self, offsets, weights=None, thresholds=(), interpolate=False):
         """Attach regions to the current test sites (mk_session_set_regions): offsets[0..G] cuts the sites, in
         their order, into G contiguous runs of at most 128; weights (one per site, default equal) make the
         regional prevalence r = sum_i omega_i p_i of joint kriging draws of the region's sites; thresholds (at
         most 8) give the posterior probability that r > u.  Needs a session created with predict_tile > 0 whose
         tile holds every test site, x_test and recorded samples.  regions() then gives the outputs of the
-        replay that makes the grids (outputs(), tile_grids()).  offsets=None detaches; so does set_test_sites."""
+        replay that makes the grids (outputs(), tile_grids()).  offsets=None detaches; so does set_test_sites.
+        interpolate=True (mk_session_set_regions_route, MK_REGIONS_INTERP) lets that replay interpolate over phi
+        wherever it would without regions (exponential models, MK_KRIG_CHEB's rule, the checks passed) and
+        serves the regions from it; the default is the exact replay.  Every attach starts from the default."""
+        if not isinstance(interpolate, (bool, np.bool_)):
+            raise TypeError("error: interpolate must be True or False")
         self._regions = None
         if offsets is None:
             check(self._lib.mk_session_set_regions(self._h, None))
@@ -404,19 +409,27 @@ class Session:
         off, _w, u, m = region_spec(offsets, self.n_test, weights, thresholds)
         check(self._lib.mk_session_set_regions(self._h, ctypes.byref(m)))
         self._regions = (int(off.size - 1), u)
+        if interpolate:
+            check(self._lib.mk_session_set_regions_route(self._h, _lib.REGIONS_INTERP))
 
     def regions(self, samples=False):
         """The areal prediction per subset after a replay (mk_session_regions; the definitions are in
         include/mk.h): {'names': mean, sd, exc_1..J, 'thresholds', 'region_predict': per subset 200 x C3,
         'subsets': per subset C3 x (2 + J), 'singular': per subset C3 counts of kept states whose factor was
         flagged, 'timing_ms'}, C3 = G q region columns (region-major); samples=True adds 'region_samples' (per
-        subset C3 x kept).  The tile must have been replayed over the current kept window since set_regions
-        (MkError otherwise)."""
+        subset C3 x kept).  'route' is the route the replay took ("exact" or "interpolated": a replay that
+        could not interpolate ran exactly) and 'check' the interpolated route's largest |interpolant - exact| over
+        the entries of the regions' covariances at its check slots (0.0 on the exact route).  The tile must have
+        been replayed over the current kept window since set_regions (MkError otherwise)."""
         G, u = self._regions if self._regions is not None else (0, np.zeros(0))
         kept = self.cfg.kept if self._window is None else self._window
         rb = RegionBuffers(self.S, self.q, G, u.size, kept, samples=samples)
         check(self._lib.mk_session_regions(self._h, ctypes.byref(rb.c)))
-        return rb.unpack(u)
+        ran, chk = ctypes.c_int32(), ctypes.c_double()
+        check(self._lib.mk_session_regions_route(self._h, None, ctypes.byref(ran), ctypes.byref(chk)))
+        out = rb.unpack(u)
+        out["route"], out["check"] = _lib.REGION_ROUTE_NAMES[ran.value], chk.value
+        return out
 
     def set_lookahead(self, mode):
         """Launch schedule before the first run: True / 1 lookahead (the next iteration's phi

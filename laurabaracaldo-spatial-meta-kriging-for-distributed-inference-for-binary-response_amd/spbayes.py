@@ -271,7 +271,8 @@ def spPairs(sp_obj, pred_coords, pred_covars, thresholds=(), start=1, end=None):
     return res
 
 
-def spRegions(sp_obj, pred_coords, pred_covars, region, weights=None, thresholds=(), start=1, end=None, samples=False):
+def spRegions(sp_obj, pred_coords, pred_covars, region, weights=None, thresholds=(), start=1, end=None, samples=False,
+              interpolate=False):
     """Areal prediction of an spMvGLM fit, on the device: `region` is an integer label per prediction site; per
     region (in ascending label order, "region.labels") and outcome a -- region column g q + a -- the prevalence
     r = sum_i omega_i p_i,a over the region's sites (omega: `weights` normalised within the region, default
@@ -280,7 +281,9 @@ def spRegions(sp_obj, pred_coords, pred_covars, region, weights=None, thresholds
     exceeds each threshold), "region.singular" (C3: kept states whose joint covariance factor was flagged),
     "region.labels", "thresholds" and, with samples=True, "region.samples" (C3 x kept); over iterations
     start..end (1-based, inclusive), kriged from the recorded chain in one replay.  A region holds at most 128
-    sites.  The sites are sorted by label (stable) for the replay.  The definitions are in include/mk.h."""
+    sites.  The sites are sorted by label (stable) for the replay.  interpolate=True serves the regions from the
+    phi-interpolated replay where it applies (Session.set_regions); "region.route" names the route that ran and
+    "region.check" its check.  The definitions are in include/mk.h."""
     ses = sp_obj.get("_session")
     if ses is None:
         raise ValueError("error: the spMvGLM fit was closed; spRegions needs its recorded chain states")
@@ -309,7 +312,7 @@ def spRegions(sp_obj, pred_coords, pred_covars, region, weights=None, thresholds
         w = w[order]
     ses.set_test_sites(ct[order], x_test=xt[rows])
     ses.set_kept_window(start, end)
-    ses.set_regions(offsets, w, thresholds)
+    ses.set_regions(offsets, w, thresholds, interpolate=interpolate)
     try:
         ses.outputs(quantiles=False, w_predict_sum=True)      # the one replay of the window
         m = ses.regions(samples=samples)
@@ -318,7 +321,7 @@ def spRegions(sp_obj, pred_coords, pred_covars, region, weights=None, thresholds
     pl = m["subsets"][0]
     res = {"region.predict": m["region_predict"][0], "region.mean": pl[:, 0].copy(), "region.sd": pl[:, 1].copy(),
            "region.exceed": pl[:, 2:].copy(), "region.singular": m["singular"][0], "region.labels": labels.tolist(),
-           "thresholds": m["thresholds"]}
+           "thresholds": m["thresholds"], "region.route": m["route"], "region.check": m["check"]}
     if samples:
         res["region.samples"] = m["region_samples"][0]
     return res

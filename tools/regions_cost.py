@@ -11,7 +11,14 @@ phi-interpolated one off).  From that one replay:
 Kind 19 holds the sum of the first three and must show no launch before the regions are attached.  One JSON
 document on stdout and, with --out, in that file.
 
-  python tools/regions_cost.py [--subsets 7] [--n 14000] [--kept 1251] [--out profiles/regions/cost.json]
+--interpolate: after that, the same session replays the window --repeats times on each route, interleaved
+(exact, interpolated, exact, ..), each replay from a fresh attach so that timing_ms and the launches are that
+replay's alone; "routes" then holds per route the wall clock, the three timing parts and kind 19's launches of
+every repeat, and for the interpolated route the route that ran, its check, the node count E (the launches less
+the check, two per chunk of kept states and the two summaries) and the largest |interpolated - exact| draw.
+
+  python tools/regions_cost.py [--subsets 7] [--n 14000] [--kept 1251] [--interpolate] [--repeats 3]
+                               [--out profiles/regions/cost.json]
 """
 import argparse
 import importlib
@@ -28,6 +35,37 @@ PKG = "laurabaracaldo-spatial-meta-kriging-for-distributed-inference-for-binary-
 THRESHOLDS = (0.2, 0.5, 0.8)
 
 
+def both_routes(mk, ses, offsets, a):
+    """--repeats replays per route on the session, interleaved; the profiler stays as main() left it."""
+    ks = mk.session.KS_REGIONS
+    sites = a.n_test // a.regions
+    fsz = a.regions * sites * sites
+    env_b = int(os.environ.get("MK_REGIONS_CHUNK") or 0)          # the library's chunk rule (include/mk.h)
+    B = max(1, min(a.kept, env_b if env_b > 0 else (1 << 30) // (8 * a.subsets * a.q * fsz)))
+    chunks = -(-a.kept // B)
+    rec = {"exact": [], "interpolated": [], "chunk_states": B, "chunks": chunks}
+    draws = {}
+    for _ in range(a.repeats):
+        for name, interp in (("exact", False), ("interpolated", True)):
+            ses.set_regions(offsets, None, THRESHOLDS, interpolate=interp)
+            before = ses.kernel_stats(ks)
+            t0 = time.perf_counter()
+            ses.outputs(quantiles=False, w_predict_sum=True)
+            wall = time.perf_counter() - t0
+            rg = ses.regions(samples=True)
+            launches = ses.kernel_stats(ks)["launches"] - before["launches"]
+            t = rg["timing_ms"].tolist()
+            row = {"replay_wall_s": wall, "cov_and_factor_ms": t[0], "draws_ms": t[1], "grids_and_planes_ms": t[2],
+                   "launches": launches, "route": rg["route"], "check": rg["check"],
+                   "singular_states": int(sum(int(x.sum()) for x in rg["singular"]))}
+            if rg["route"] == "interpolated":
+                row["nodes_E"] = launches - (1 + 2 * chunks + 2)
+            rec[name].append(row)
+            draws[name] = rg["region_samples"]
+    rec["max_abs_draw_difference"] = float(max(np.abs(x - y).max() for x, y in zip(draws["exact"], draws["interpolated"])))
+    return rec
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--subsets", type=int, default=7)
@@ -37,6 +75,8 @@ def main():
     ap.add_argument("--regions", type=int, default=10)
     ap.add_argument("--kept", type=int, default=1251)
     ap.add_argument("--warmup", type=int, default=50)
+    ap.add_argument("--interpolate", action="store_true", help="time both routes on the one session")
+    ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     mk = importlib.import_module(PKG)
@@ -69,6 +109,7 @@ def main():
         pv = ses.kernel_stats(mk.session.KS_PRED_VAR)
         rg = ses.regions()
         kind19 = ses.kernel_stats(mk.session.KS_REGIONS)
+        routes = both_routes(mk, ses, offsets, a) if a.interpolate else None
     t = rg["timing_ms"].tolist()
     rec = {"geometry": {"subsets": K, "sites_per_subset": a.n // K, "q": q, "n_test": a.n_test, "regions": a.regions,
                         "sites_per_region": a.n_test // a.regions, "kept_states": a.kept, "thresholds": list(THRESHOLDS)},
@@ -80,6 +121,8 @@ def main():
            "cov_over_pred_var": t[0] / max(pv["ms"] - before["ms"], 1e-30),
            "singular_states": int(sum(int(x.sum()) for x in rg["singular"])),
            "first_subset_planes": {n: rg["subsets"][0][:, i].tolist() for i, n in enumerate(rg["names"])}}
+    if routes is not None:
+        rec["routes"] = routes
     text = json.dumps(rec, indent=1)
     print(text, flush=True)
     if a.out:
