@@ -706,6 +706,43 @@ int mk_glm_binomial_link(const double* y, const double* weights, const double* x
                          int32_t link, double epsilon, int32_t maxit, double* coef, double* vcov,
                          int32_t* iters, int32_t device);
 
+/* ---- empirical variogram: all pairs of n sites, before the fit (the phi prior) and after it (misfit) ----
+ * The reference chooses phi's start and prior by hand (MK.R:60-63: an effective range of 0.5 on the unit
+ * square, Unif(3/0.75, 3/0.25)); the variogram of the start-value glm's residuals is what such a choice is
+ * read from, and the variogram of held-out residuals is what is left of spatial structure after a fit.  For
+ * q >= 2 the cross-variograms are the empirical counterpart of K = A A'.  Every pair is visited: nothing
+ * is subsampled.
+ * coords is n x 2 column-major, z location-major (site i, outcome a at i q + a).  The T = q (q + 1) / 2
+ * outcome pairs (a >= b) come in the lower-triangle column-major order of A and K: (0,0), (1,0), ..,
+ * (q-1,0), (1,1), ..; the diagonal entries are the direct semivariograms, the others the cross-variograms.
+ *   s = n_bins / max_dist, divided once on the host
+ *   for each unordered pair i < j:  d = sqrt(dx dx + dy dy) with dx = x_i - x_j, dy = y_i - y_j (dist2d's
+ *     expression, no contraction), k = floor(d s); the pair is counted iff k < n_bins, so the bins are
+ *     half-open, [k/s, (k+1)/s); coincident sites (d = 0) fall in bin 0; a site is never paired with itself
+ *     and each unordered pair is counted once
+ *   count[k]    = N_k
+ *   dist[k]     = (sum of d) / N_k
+ *   gamma_ab[k] = (sum of (z_a(i) - z_a(j)) (z_b(i) - z_b(j))) / (2 N_k), Matheron's estimator
+ * An empty bin has count 0 and NaN in dist and gamma.  The sums are fp64 in a fixed order -- a lane's pairs
+ * in (tile, column) order, the lanes of a workgroup in lane order, the workgroups in index order, the tiles
+ * dealt to a number of workgroups fixed by n alone -- and the counts are integers, so two calls with the
+ * same arguments return the same bytes on any placement; there are no floating-point atomics.
+ * MK_E_ARG, before any device is touched and with the message in mk_last_error: a null pointer, n < 2 (or
+ * above 2^24), q outside 1 .. MK_VG_MAXQ, n_bins outside 1 .. MK_VG_MAXBINS, max_dist not finite or not > 0,
+ * a coordinate or z value that is not finite (the message names the first such index). */
+#define MK_VG_MAXBINS 64
+#define MK_VG_MAXQ 4
+#define MK_VG_EDGE 256    /* tile edge of the pair kernel (mk_variogram_tile_edge) */
+typedef struct mk_variogram {
+  int64_t* count;   /* [n_bins]      pairs in the bin                                   */
+  double*  dist;    /* [n_bins]      mean distance of the bin's pairs, NaN if empty     */
+  double*  gamma;   /* [T][n_bins]   T = q(q+1)/2, NaN if empty                         */
+  double   ms;      /* out: device time of the launches, by one event pair             */
+} mk_variogram;
+int mk_variogram_compute(const double* coords, int64_t n, const double* z, int32_t q, int32_t n_bins,
+                         double max_dist, mk_variogram* out, int32_t device);
+int32_t mk_variogram_tile_edge(void);
+
 /* ---- partition (MK.R:15-41) with R's own RNG stream, host side ----
  * After `set.seed(seed)` under R >= 3.6.0 defaults (Mersenne-Twister, Rejection sampling),
  * the reference's loop `index.part[[i]] <- sample(a, n.part[i]); a <- setdiff(a, ...)`.

@@ -11,6 +11,7 @@ from .session import (SamplerConfig, Session, chain_diagnostics, cholesky_batche
 from .spbayes import spDiag, spDiagnostics, spMaps, spMvGLM, spPairs, spPredict, spRegions, spValidate  # noqa: F401
 from .glm import glm_binomial  # noqa: F401
 from .post import combine_median  # noqa: F401
+from .variogram import (fit_exponential, glm_residuals, residual_variogram, suggest_phi, variogram)  # noqa: F401
 from .metakriging import (combine_predictive, combine_regions, combine_results, convergence_report, meta_fit,  # noqa: F401
                           partition, partitioned_spMvGLM, posterior_summary, start_values, subset_data, validation_report)
 from .node import meta_fit_node  # noqa: F401

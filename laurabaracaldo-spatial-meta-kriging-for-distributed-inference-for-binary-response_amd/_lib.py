@@ -38,6 +38,8 @@ REGION_MAXM = 128      # MK_REGION_MAXM: sites per region at most
 REGION_BASE_NAMES = ["mean", "sd"]     # the region planes before exc_1..J
 REGIONS_EXACT, REGIONS_INTERP = 0, 1    # MK_REGIONS_EXACT, MK_REGIONS_INTERP: the routes of the areal prediction
 REGION_ROUTE_NAMES = ["exact", "interpolated"]
+VG_MAXBINS = 64        # MK_VG_MAXBINS: variogram bins at most
+VG_MAXQ = 4            # MK_VG_MAXQ: outcomes of a variogram at most
 
 _dp = ctypes.POINTER(ctypes.c_double)
 _ip = ctypes.POINTER(ctypes.c_int32)
@@ -128,6 +130,10 @@ class Regions(ctypes.Structure):
     _fields_ = [("region_predict", _dp), ("planes", _dp), ("region_samples", _dp), ("singular", _ip), ("timing_ms", _dp)]
 
 
+class Variogram(ctypes.Structure):
+    _fields_ = [("count", ctypes.POINTER(ctypes.c_int64)), ("dist", _dp), ("gamma", _dp), ("ms", ctypes.c_double)]
+
+
 # int (*mk_progress_fn)(void* user, int32_t iterations, int32_t n_samples)
 PROGRESS_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32)
 
@@ -212,6 +218,9 @@ EXPORTS = {
                                             ctypes.c_double, ctypes.c_int32, _dp, _dp, _ip, ctypes.c_int32]),
     "mk_glm_binomial": (ctypes.c_int, [_dp, _dp, _dp, ctypes.c_int64, ctypes.c_int32, ctypes.c_double,
                                        ctypes.c_int32, _dp, _dp, _ip, ctypes.c_int32]),
+    "mk_variogram_compute": (ctypes.c_int, [_dp, ctypes.c_int64, _dp, ctypes.c_int32, ctypes.c_int32, ctypes.c_double,
+                                            ctypes.POINTER(Variogram), ctypes.c_int32]),
+    "mk_variogram_tile_edge": (ctypes.c_int32, []),
     "mk_correlation_batched": (ctypes.c_int, [_dp, ctypes.c_int32, ctypes.c_int32, _dp, _dp, ctypes.c_int32, _dp,
                                               ctypes.c_int32]),
     "mk_correlation_cross_batched": (ctypes.c_int, [_dp, ctypes.c_int32, ctypes.c_int32, _dp, ctypes.c_int32, _dp, _dp,

@@ -87,6 +87,20 @@ def main():
                          "prefix); one more JSON line, {\"pairs\": the files, per pair the share of sites with "
                          "combined P(p_a > p_b) >= 0.95}; one process (plain or --devices)")
     ap.add_argument("--pairs-out", default="pairs", help="prefix of the files --pairs saves")
+    ap.add_argument("--variogram", type=int, nargs="?", const=15, default=None, metavar="N_BINS",
+                    help="before the fit, the empirical variogram of the start-value glm's Pearson residuals over "
+                         "all pairs of sites, on the device (15 bins up to a third of the bounding box's diagonal; "
+                         "at most 64): the table per outcome on stderr, saved as n_bins x (4 + T) .npy (from, to, "
+                         "pairs, h, gamma per outcome pair; --variogram-out), and one more JSON line, {\"variogram\": "
+                         "the exponential fits and the phi start and prior they suggest}; with --validate also the "
+                         "variogram of the held-out residuals of the combined grid, {\"heldout_variogram\": ...}: "
+                         "structure left there is misfit.  Not with --devices")
+    ap.add_argument("--variogram-out", default="variogram.npy", help="where --variogram saves its table")
+    ap.add_argument("--phi-from-variogram", action="store_true",
+                    help="start phi at the residual variogram's fitted decay and put its uniform prior around the fitted "
+                         "range (suggest_phi: the reference's own ratios) instead of MK.R:60-63's 3/0.5 and "
+                         "Unif(3/0.75, 3/0.25); implies --variogram.  Off by default: without it nothing about the fit "
+                         "changes")
     a = ap.parse_args()
     a.map_thresholds = None if a.maps is None else [float(u) for u in a.maps.split(",") if u.strip()]
     a.pair_thresholds = None if a.pairs is None else [float(u) for u in a.pairs.split(",") if u.strip()]
@@ -98,7 +112,11 @@ def main():
             c[k_cfg] = v
     if a.pair_thresholds is not None and c["q"] < 2:
         ap.error(f"--pairs needs a multivariate config: --config {a.config} has q = {c['q']} (--config 4 is q = 3)")
+    if a.phi_from_variogram and a.variogram is None:
+        a.variogram = 15
     if a.devices is not None:
+        if a.variogram is not None:
+            ap.error("--variogram and --phi-from-variogram run in the plain path (one process per GPU), not with --devices")
         return node_main(a, c)
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -129,8 +147,13 @@ def main():
     n_part, index_part = mk.partition(n, K, seed=a.seed, method=a.partition)                     # MK.R:15-41
     beta0, bt = mk.start_values(d["y"], d["x"], 1.0, q, device=local)         # MK.R:53-55
     p = d["x"].shape[1]
+    vario, phi_kw = None, {}
+    if a.variogram is not None:               # every rank: the suggestion is a function of the data alone
+        vario = residual_variogram_before(mk, d, q, a, local, report=rank == 0)
+        if a.phi_from_variogram:
+            phi_kw = dict(phi_starting=vario["suggestion"]["starting"], phi_unif=vario["suggestion"]["unif"])
     cfg = mk.SamplerConfig(q, p, beta0, bt, cov_model=c["cov"], n_batch=c["n_batch"], batch_length=c["batch_length"],
-                           seed=a.seed, predict_tile=c.get("predict_tile", 0))
+                           seed=a.seed, predict_tile=c.get("predict_tile", 0), **phi_kw)
     lo, hi = dmod.shard_range(K, world, rank)
     subs = [mk.subset_data(d["y"], d["x"], 1.0, d["coords"], q, index_part[i]) for i in range(lo, hi)]
     t["setup_s"] = time.perf_counter() - t1
@@ -285,8 +308,12 @@ def main():
             print(json.dumps({"diagnostics": mk.convergence_report(diag)}), flush=True)
         if a.criteria:
             print(json.dumps({"criteria": dict(zip(crit["names"], crit["total"].tolist()))}), flush=True)
+        if vario is not None:
+            print(json.dumps({"variogram": vario["line"]}), flush=True)
         if a.validate and result3 is not None:
             print(json.dumps({"validation": validation_line(mk, result3, d, scores, local)}), flush=True)
+            if a.variogram is not None:
+                print(json.dumps({"heldout_variogram": heldout_variogram_line(mk, result3, d, a, local)}), flush=True)
         if a.map_thresholds is not None and result3 is not None:
             w, p = (mk.map_grid(np.asarray(g), u, device=local) for g, u in ((result2, ()), (result3, a.map_thresholds)))
             names = ["w_" + k for k in w["names"]] + ["p_" + k for k in p["names"][:2]] + p["names"][2:]
@@ -320,6 +347,53 @@ def validation_line(mk, result3, d, scores, device):
     if scores is not None:
         line["median_subset"] = mk.metakriging.median_subset_row(scores)
     return line
+
+
+def finite_or_none(v):
+    """A list for a JSON line: None where a bin is empty (NaN)."""
+    return [float(x) if np.isfinite(x) else None for x in v]
+
+
+def variogram_fits(mk, vg):
+    """Per outcome the exponential fit of its direct variogram, and the table on stderr."""
+    vmod = importlib.import_module(PKG + ".variogram")
+    fits = []
+    for t, (i, j) in enumerate(vg["pairs"]):
+        if i == j:
+            print(vmod.table(vg, pair=t), file=sys.stderr, flush=True)
+            fits.append(mk.fit_exponential(vg, pair=t))
+    return fits
+
+
+def residual_variogram_before(mk, d, q, a, device, report):
+    """--variogram before the fit: the variogram of the start-value glm's Pearson residuals over all pairs of
+    sites, its table (n_bins x (4 + T): from, to, pairs, h, gamma per outcome pair) saved, the fits and the phi
+    start and prior they suggest."""
+    n = d["coords"].shape[0]
+    r = mk.glm_residuals(d["y"], d["x"], 1.0, device=device)
+    vg = mk.variogram(d["coords"], r.reshape(n, q), n_bins=a.variogram, device=device)
+    if not report:
+        return {"suggestion": mk.suggest_phi(vg), "line": None}
+    fits = variogram_fits(mk, vg)
+    sug = mk.suggest_phi(vg, fits=fits)
+    np.save(a.variogram_out, np.column_stack([vg["edges"][:-1], vg["edges"][1:], vg["count"], vg["h"], vg["gamma"].T]))
+    line = {"file": a.variogram_out, "n_bins": vg["n_bins"], "max_dist": vg["max_dist"], "pairs": int(vg["count"].sum()),
+            "device_ms": vg["ms"], "fits": fits, "phi_starting": sug["starting"].tolist(),
+            "phi_unif": [sug["unif"][0].tolist(), sug["unif"][1].tolist()], "used_for_the_fit": bool(a.phi_from_variogram)}
+    print(f"suggested phi start {line['phi_starting']} and uniform prior {line['phi_unif']} (exploratory: a residual "
+          "variogram of binary data is noisy and attenuated)", file=sys.stderr, flush=True)
+    return {"suggestion": sug, "line": line}
+
+
+def heldout_variogram_line(mk, result3, d, a, device):
+    """--variogram with --validate: the variogram of the held-out Pearson residuals of the combined grid's
+    pmean (score_grid's pointwise column); spatial structure left in it is misfit."""
+    pmean = mk.score_grid(np.asarray(result3), d["y_test"], pointwise=True, device=device)["pointwise"][:, 0]
+    vg = mk.residual_variogram(d["coords_test"], d["y_test"], 1.0, pmean, n_bins=a.variogram, device=device)
+    fits = variogram_fits(mk, vg)
+    return {"n_bins": vg["n_bins"], "max_dist": vg["max_dist"], "pairs": int(vg["count"].sum()), "device_ms": vg["ms"],
+            "count": vg["count"].tolist(), "h": finite_or_none(vg["h"]), "gamma": [finite_or_none(g) for g in vg["gamma"]],
+            "fits": fits}
 
 
 def maps_line(planes, names, a):
