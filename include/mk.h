@@ -814,6 +814,44 @@ void mk_shutdown(void);
  * environment variable MK_WATCHDOG=<seconds> sets it at load). */
 int mk_set_watchdog(int32_t seconds);
 
+/* ---- sessions from a recorded chain ----
+ * Everything the kriging replay and the result sinks read of a fit is what a fit reports: samples
+ * (beta | lower-tri K | phi | nu per iteration) and w_samples (w = A u).  mk_session_import_chain rebuilds the
+ * kept-state record from them -- per kept state A = chol(K) with a positive diagonal, theta (A's lower triangle
+ * with log diagonal | logit phi | logit nu), u_i = A^-1 w_i per site and z_h = L_h^-1 u_h with L_h the Cholesky
+ * factor of R(phi_h, nu_h) -- so a chain saved by an earlier process, or made elsewhere (the CPU oracle, another
+ * machine), is replayed at any test sites and through every sink without running it again.
+ *
+ * Valid on a session as mk_session_create left it (no iteration run, nothing imported, not poisoned) that keeps
+ * chain states: predict_tile > 0, and no test sites or more test sites than the tile.  The checks run on the
+ * host before the device is touched, and each refusal (MK_E_ARG) names the global subset index, the 1-based
+ * iteration and the column or row: a null pointer, n_w out of range, a value that is not finite, a kept phi (nu
+ * under Matern) that is not strictly inside its prior, a kept K that is not positive definite.  A kept state
+ * whose R(phi_h, nu_h) meets a pivot that is not > 0 on the device is MK_E_ARG naming subset, outcome and
+ * iteration, and the session is left as created.  Out of memory is MK_E_NOMEM; every buffer of the import other
+ * than the record is freed before the call returns.
+ *
+ * Afterwards the session is one whose chain is complete: mk_session_iteration returns n.samples, and the
+ * outputs, grids, tile grids, test sites, covariates, kept windows and every sink work as after mk_session_run
+ * (the criteria by their replay route, which needs record_w; in-chain criteria are refused).  samples and, with
+ * record_w, w_samples come back from mk_session_outputs as the bytes that went in; mk_session_notpd_counts
+ * returns zeros.  The imported z is computed from w, the live chain's is updated incrementally: the two sessions
+ * agree to rounding.  mk_session_run, mk_session_chain_state and mk_session_set_lookahead on an imported
+ * session are MK_E_ARG, and so is asking for acceptance when none was imported. */
+typedef struct mk_chain {
+  const double* samples;     /* [n_subsets] x (n_samples x P) column-major, the layout of mk_outputs.samples   */
+  const double* w_samples;   /* [n_subsets] x ((n_s q) x n_w) column-major: the LAST n_w iterations' w           */
+  int32_t n_w;               /* kept <= n_w <= n_samples; must be n_samples when cfg.record_w                    */
+  const double* acceptance;  /* optional, the layout of mk_outputs.acceptance; NULL: none recorded               */
+} mk_chain;
+int mk_session_import_chain(mk_session* s, const mk_chain* c);
+int32_t mk_session_imported(const mk_session* s);          /* 1 after a successful import */
+/* What the import cost: the (subset, outcome) factorisations it made (one per run of consecutive kept states
+ * with the same (phi_h, nu_h), summed over the pairs), the milliseconds of the factor refreshes (candidate,
+ * Cholesky, inverse) and of the z = W u launches (k_import_z), by device events.  Any pointer may be NULL;
+ * MK_E_ARG unless the session was imported. */
+int mk_session_import_stats(const mk_session* s, int64_t* factorisations, double* ms_factor, double* ms_z);
+
 const char* mk_last_error(void);
 int mk_device_count(void);
 /* Free and total HBM of a device (hipMemGetInfo), e.g. to size shards or check for leaks. */

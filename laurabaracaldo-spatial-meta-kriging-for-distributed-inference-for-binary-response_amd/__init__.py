@@ -8,11 +8,11 @@ this package is the host-side mirror of the reference's R interface
 from ._lib import MkError, load  # noqa: F401
 from .session import (SamplerConfig, Session, chain_diagnostics, cholesky_batched, combine,  # noqa: F401
                       correlation_batched, correlation_cross_batched, map_grid, score_grid)
-from .spbayes import spDiag, spDiagnostics, spMaps, spMvGLM, spPairs, spPredict, spRegions, spValidate  # noqa: F401
+from .spbayes import load_fit, spDiag, spDiagnostics, spMaps, spMvGLM, spPairs, spPredict, spRegions, spValidate  # noqa: F401
 from .glm import glm_binomial  # noqa: F401
 from .post import combine_median  # noqa: F401
 from .variogram import (fit_exponential, glm_residuals, residual_variogram, suggest_phi, variogram)  # noqa: F401
 from .metakriging import (combine_predictive, combine_regions, combine_results, convergence_report, meta_fit,  # noqa: F401
                           partition, partitioned_spMvGLM, posterior_summary, start_values, subset_data, validation_report)
 from .node import meta_fit_node  # noqa: F401
-from . import synthetic  # noqa: F401
+from . import fitfile, synthetic  # noqa: F401

@@ -134,6 +134,10 @@ class Variogram(ctypes.Structure):
     _fields_ = [("count", ctypes.POINTER(ctypes.c_int64)), ("dist", _dp), ("gamma", _dp), ("ms", ctypes.c_double)]
 
 
+class Chain(ctypes.Structure):
+    _fields_ = [("samples", _dp), ("w_samples", _dp), ("n_w", ctypes.c_int32), ("acceptance", _dp)]
+
+
 # int (*mk_progress_fn)(void* user, int32_t iterations, int32_t n_samples)
 PROGRESS_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32)
 
@@ -196,6 +200,9 @@ EXPORTS = {
     "mk_session_profile_every": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32]),
     "mk_session_kernel_stats": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(ctypes.c_int64),
                                                _dp, _dp]),
+    "mk_session_import_chain": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(Chain)]),
+    "mk_session_imported": (ctypes.c_int32, [ctypes.c_void_p]),
+    "mk_session_import_stats": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64), _dp, _dp]),
     "mk_session_destroy": (None, [ctypes.c_void_p]),
     "mk_session_count": (ctypes.c_int32, []),
     "mk_fit_predict_batched": (ctypes.c_int, [ctypes.POINTER(Problem), ctypes.POINTER(Config), ctypes.POINTER(Outputs)]),

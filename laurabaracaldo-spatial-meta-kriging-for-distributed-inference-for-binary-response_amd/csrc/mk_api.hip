@@ -692,6 +692,12 @@ static int initial_state(mk_session* s) {
   return 0;
 }
 
+int mk::chain_reinit(mk_session* s) {
+  int rc;
+  if ((rc = reset_factor_state(s))) return rc;
+  return initial_state(s);
+}
+
 extern "C" int mk_session_create(const mk_problem* pr, const mk_config* c, mk_session** out) {
   if (!out) return set_err(MK_E_ARG, "null out");
   *out = nullptr;
@@ -729,6 +735,8 @@ extern "C" int mk_session_create(const mk_problem* pr, const mk_config* c, mk_se
 extern "C" int mk_session_run(mk_session* s, int32_t n_iter) {
   if (!s) return set_err(MK_E_ARG, "null session");
   if (s->poisoned) return poisoned_err(s);
+  if (s->imp.done)
+    return set_err(MK_E_ARG, "the session holds an imported chain, which is complete: mk_session_run cannot continue it");
   MK_ENTRY_DEVICE(s->device);
   if (n_iter < 0 || s->iter + n_iter > s->md.n_samples) return set_err(MK_E_ARG, "n_iter beyond n.samples");
   if (s->la.on && !s->la.c) {
@@ -843,6 +851,8 @@ extern "C" int mk_session_chain_state(mk_session* s, int32_t subset, double* bet
                                       double* tune, double* accept) {
   if (!s) return set_err(MK_E_ARG, "null session");
   if (s->poisoned) return poisoned_err(s);
+  if (s->imp.done)
+    return set_err(MK_E_ARG, "the session holds an imported chain: it has the recorded states, not a sampler's state to resume");
   if (subset < 0 || subset >= s->S) return set_err(MK_E_ARG, "subset out of range");
   MK_ENTRY_DEVICE(s->device);
   const Model& md = s->md;
@@ -872,6 +882,8 @@ extern "C" int mk_session_notpd_counts(mk_session* s, int64_t* out) {
 extern "C" int mk_session_set_lookahead(mk_session* s, int32_t mode) {
   if (!s) return set_err(MK_E_ARG, "null session");
   if (mode < -1 || mode > 1) return set_err(MK_E_ARG, "lookahead mode must be -1 (auto), 0 or 1");
+  if (s->imp.done)
+    return set_err(MK_E_ARG, "the session holds an imported chain: no iteration will run, so there is no schedule to set");
   if (s->iter > 0) return set_err(MK_E_ARG, "the schedule is fixed once the chain has started");
   if (mode == 1 && !s->la.ok)
     return set_err(MK_E_ARG, "lookahead needs the exponential model on one stream group");
@@ -1036,6 +1048,8 @@ extern "C" int mk_session_outputs(mk_session* s, mk_outputs* o) {
   const bool want_p = o->p_predict || o->p_pred_samples || o->p_predict_sum;
   if ((o->parameters || o->w_predict || o->w_pred_samples || want_p) && !done)
     return set_err(MK_E_ARG, "quantile/predictive outputs need all n.samples iterations");
+  if (o->acceptance && s->imp.done && !s->imp.acc)
+    return set_err(MK_E_ARG, "acceptance: the imported chain came without acceptance rates (mk_chain.acceptance was NULL)");
   if (want_p && !s->d_xt)
     return set_err(MK_E_ARG, "p_predict / p_pred_samples / p_predict_sum need x_test (mk_problem.x_test or "
                              "mk_session_set_test_covars)");

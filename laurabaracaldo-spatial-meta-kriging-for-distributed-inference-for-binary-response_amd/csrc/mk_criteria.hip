@@ -252,6 +252,9 @@ void mk::crit_drain(mk_session* s, bool price) {
 
 extern "C" int mk_session_set_criteria(mk_session* s, int32_t enable) {
   if (!s) return set_err(MK_E_ARG, "null session");
+  if (s->imp.done)
+    return set_err(MK_E_ARG, "in-chain criteria need the chain to run here: an imported session serves mk_session_criteria "
+                             "by replaying its recorded chain (record_w)");
   if (s->iter > 0) return set_err(MK_E_ARG, "in-chain criteria are switched before the first mk_session_run only");
   const bool on = enable != 0;
   if (on == s->crit.on) return 0;

@@ -12,6 +12,7 @@
 //   mk_maps.hip      posterior maps (mean, sd, exceedance of p(y = 1)): the kernel, the entry points
 //   mk_pairs.hip     cross-outcome prediction (co-occurrence and contrast of two outcomes): the kernels, the entry points
 //   mk_regions.hip   areal prediction (regional prevalence from joint kriging draws): the kernels, the entry points
+//   mk_import.hip    sessions from a recorded chain: the kernels, the upload, the entry points
 //
 // What the six result sinks above share is here and in mk_tilefill.hpp: EventTimer (their launches' price),
 // TileFill (which tiles a tiled session's buffer holds, over which kept window), results_entry (the checks a
@@ -348,6 +349,15 @@ struct RegionInterp {
   int E = 0;
 };
 
+// mk_import.hip.  A chain imported by mk_session_import_chain, and what the import cost.
+struct Import {
+  bool done = false;           // the record (z, theta, A), samples and w_samples are an imported chain's
+  bool acc = false;            // the chain came with acceptance rates
+  long factorisations = 0;     // (subset, outcome) factor refreshes
+  double ms_factor = 0.0, ms_z = 0.0;
+  int batch = 0;               // states per pass over W (k_import_z's B)
+};
+
 }  // namespace mk
 
 struct mk_session {
@@ -389,7 +399,8 @@ struct mk_session {
   mk::Maps maps;
   mk::Pairs pairs;
   mk::Regions regions;
-  std::vector<double> ct_h;       // the current test sites on the host, x then y (the regions' coincidence check)
+  mk::Import imp;
+  std::vector<double> ct_h;      // the current test sites on the host, x then y (the regions' coincidence check)
   mk_diagnostics diag_sink{};           // mk_session_set_diagnostics: filled by every tile replay while diag_on
   bool diag_on = false;
   hipError_t launch_err = hipSuccess;   // first failed kernel launch of a run
@@ -529,6 +540,8 @@ int upload_col_chunks(const double* h, long n_rows, long n_cols, long chunk, dou
 Model model_view(const Model& m, int s0, int S);   // subsets [s0, s0 + S) of the shard's arrays
 MatSet matset_view(const MatSet& m, int s0);
 int setup_groups(mk_session* s, int n_groups);
+// The factors, W, z and the statistics as mk_session_create left them (a failed import used them as scratch).
+int chain_reinit(mk_session* s);
 // A block of grids [S][Ct][200] in HBM to the host, on the session stream and not waited for: every
 // subset's columns into [col0, col0 + Ct) of its [C][200] array at h_each, and their sequential sum
 // (k_combine into dsum, Ct * 200 doubles) into the same columns of h_sum ([C][200]).  Either host

@@ -229,6 +229,53 @@ class Session:
         check(self._lib.mk_session_notpd_counts(self._h, out.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))))
         return out
 
+    def import_chain(self, samples, w_samples, acceptance=None):
+        """A recorded chain into a session that never ran (mk_session_import_chain): afterwards the session
+        serves outputs(), tile_grids(), set_test_sites() and every sink as one whose run() is complete.
+        samples: per subset n_samples x P (p.beta.theta.samples: beta | lower-tri K | phi | nu), a list or one
+        stacked array; w_samples: per subset (n_s q) x n_w, the w of the LAST n_w iterations (p.w.samples or
+        its trailing columns; kept <= n_w <= n_samples, and n_samples when the session records w);
+        acceptance: per subset n_batch x (P + 1), or None.  The session must keep chain states
+        (predict_tile > 0, and no test sites or more than the tile).  MkError names the subset, the
+        iteration and the column or row of a value the import refuses."""
+        cfg = self.cfg
+        sm = [np.asarray(a, dtype=np.float64) for a in samples]
+        ws = [np.asarray(a, dtype=np.float64) for a in w_samples]
+        if len(sm) != self.S or len(ws) != self.S:
+            raise ValueError(f"error: import_chain needs samples and w_samples of {self.S} subsets")
+        for i, a in enumerate(sm):
+            if a.shape != (cfg.n_samples, cfg.P):
+                raise ValueError(f"error: samples of subset {i} must be n_samples x P = {cfg.n_samples} x {cfg.P}, not {a.shape}")
+        n_w = ws[0].shape[1] if ws[0].ndim == 2 else -1
+        for i, a in enumerate(ws):
+            if a.ndim != 2 or a.shape != (int(self.n_part[i]) * cfg.q, n_w):
+                raise ValueError(f"error: w_samples of subset {i} must be (n_s q) x n_w = {int(self.n_part[i]) * cfg.q} x {n_w}, "
+                                 f"not {a.shape}")
+        c = _lib.Chain()
+        hs = _f64(np.stack([a.T for a in sm]))
+        hw = _f64(np.concatenate([a.T.ravel() for a in ws]))
+        c.samples, c.w_samples, c.n_w = dptr(hs), dptr(hw), int(n_w)
+        ha = None
+        if acceptance is not None:
+            ac = [np.asarray(a, dtype=np.float64) for a in acceptance]
+            if len(ac) != self.S or any(a.shape != (cfg.n_batch, cfg.P + 1) for a in ac):
+                raise ValueError(f"error: acceptance must be n_batch x (P + 1) = {cfg.n_batch} x {cfg.P + 1} per subset")
+            ha = _f64(np.stack([a.T for a in ac]))
+        c.acceptance = dptr(ha)
+        check(self._lib.mk_session_import_chain(self._h, ctypes.byref(c)))
+
+    @property
+    def imported(self):
+        """True once import_chain succeeded: the session replays a recorded chain, it cannot run()."""
+        return bool(self._lib.mk_session_imported(self._h))
+
+    def import_stats(self):
+        """What the import cost (mk_session_import_stats): the (subset, outcome) factorisations it made and the
+        milliseconds of the factor refreshes and of the z = W u launches."""
+        n, a, b = ctypes.c_int64(), ctypes.c_double(), ctypes.c_double()
+        check(self._lib.mk_session_import_stats(self._h, ctypes.byref(n), ctypes.byref(a), ctypes.byref(b)))
+        return dict(factorisations=n.value, ms_factor=a.value, ms_z=b.value)
+
     def set_test_sites(self, coords_test, x_test=None):
         """Kriging sites for the next outputs() of a session created with predict_tile > 0
         (its kept chain states were recorded during the run): spPredict without refitting.

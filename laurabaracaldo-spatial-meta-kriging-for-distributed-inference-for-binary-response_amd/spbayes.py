@@ -21,6 +21,7 @@ a fit that fused the kriging into iterations start..end.
 """
 import numpy as np
 
+from . import fitfile
 from .session import SamplerConfig, Session
 
 PREDICT_TILE = 65536   # test sites per kriging pass in spPredict (device buffers per pass)
@@ -90,6 +91,14 @@ class SpMvGLMFit(dict):
     ``close()`` -- or the end of a ``with`` block, or garbage collection.  Close fits you no
     longer predict from when fitting many subsets in a loop: each holds its factors in HBM."""
 
+    def save(self, path):
+        """The fit into one file (fitfile.save_session): R's save() of an spMvGLM object.  load_fit(path) gives
+        an object that serves spPredict and the other sp* calls in a later process, without running the chain."""
+        ses = self.get("_session")
+        if ses is None:
+            raise ValueError("error: the spMvGLM fit was closed; save() needs its session")
+        fitfile.save_session(ses, path)
+
     def close(self):
         ses = self.pop("_session", None)
         if ses is not None:
@@ -124,6 +133,25 @@ def spMvGLM(formula, coords, weights, starting, tuning, priors, amcmc, cov_model
     fit["acceptance"] = out["acceptance"][0]
     fit["_session"] = ses                    # closed when the fit object is collected
     fit["_n_samples"] = cfg.n_samples
+    return fit
+
+
+def load_fit(path, device=0):
+    """The spMvGLM fit SpMvGLMFit.save wrote, on `device`: the same keys, and a session rebuilt from the file's
+    chain (fitfile.load_session), so spPredict, spDiag, spDiagnostics, spValidate, spMaps, spPairs and spRegions
+    serve it unchanged.  p.beta.theta.samples and p.w.samples are the saved bytes; the kriging draws agree with
+    the original fit's to rounding (the record's z is recomputed from w)."""
+    a = fitfile.read(path)
+    if a["n_part"].shape[0] != 1:
+        raise ValueError(f"error: load_fit reads the file of one spMvGLM fit; '{path}' holds {a['n_part'].shape[0]} subsets "
+                         "(fitfile.load_session loads those)")
+    ses = fitfile.session_from(a, device=device)
+    fit = SpMvGLMFit()
+    fit["p.beta.theta.samples"] = a["samples"][0]
+    fit["p.w.samples"] = a["w_samples"]
+    fit["acceptance"] = a["acceptance"][0]
+    fit["_session"] = ses
+    fit["_n_samples"] = ses.cfg.n_samples
     return fit
 
 

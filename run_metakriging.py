@@ -101,6 +101,16 @@ def main():
                          "range (suggest_phi: the reference's own ratios) instead of MK.R:60-63's 3/0.5 and "
                          "Unif(3/0.75, 3/0.25); implies --variogram.  Off by default: without it nothing about the fit "
                          "changes")
+    ap.add_argument("--save-fit", default=None, metavar="DIR",
+                    help="after the chain, save the session (data, configuration, p.beta.theta.samples, p.w.samples) as "
+                         "DIR/session_0.npz (fitfile.save_session): the session then keeps its chain states and records w "
+                         "(a kriging tile even where the config has none) instead of fusing the kriging into the kept "
+                         "iterations.  One process; not with --devices.  Off by default: without it nothing about a run "
+                         "changes")
+    ap.add_argument("--from-fit", default=None, metavar="DIR",
+                    help="skip the partition, the start-value glm and the MCMC: load DIR/session_0.npz (--save-fit), "
+                         "krige this run's test sites from its recorded chain, combine and summarise as usual.  One "
+                         "process; not with --devices")
     a = ap.parse_args()
     a.map_thresholds = None if a.maps is None else [float(u) for u in a.maps.split(",") if u.strip()]
     a.pair_thresholds = None if a.pairs is None else [float(u) for u in a.pairs.split(",") if u.strip()]
@@ -114,7 +124,11 @@ def main():
         ap.error(f"--pairs needs a multivariate config: --config {a.config} has q = {c['q']} (--config 4 is q = 3)")
     if a.phi_from_variogram and a.variogram is None:
         a.variogram = 15
+    if a.save_fit is not None and a.from_fit is not None:
+        ap.error("--save-fit and --from-fit: a run either makes the chain and saves it, or loads it")
     if a.devices is not None:
+        if a.save_fit is not None or a.from_fit is not None:
+            ap.error("--save-fit and --from-fit run in the plain path (one process), not with --devices")
         if a.variogram is not None:
             ap.error("--variogram and --phi-from-variogram run in the plain path (one process per GPU), not with --devices")
         return node_main(a, c)
@@ -126,6 +140,10 @@ def main():
         ap.error("--criteria runs in one process: plain, or over several GPUs with --devices")
     if a.pair_thresholds is not None and world > 1:
         ap.error("--pairs runs in one process: plain, or over several GPUs with --devices")
+    if (a.save_fit is not None or a.from_fit is not None) and world > 1:
+        ap.error("--save-fit and --from-fit run in one process")
+    if a.from_fit is not None and a.variogram is not None:
+        ap.error("--variogram looks at the start-value glm's residuals, which --from-fit skips")
     local = int(os.environ.get("LOCAL_RANK", "0"))
     # the combined grid of p(y = 1), result3; the pairs need x.test on the device as it does
     need_p = a.validate or a.map_thresholds is not None or a.pair_thresholds is not None
@@ -144,38 +162,58 @@ def main():
     t["data_s"] = time.perf_counter() - t0
 
     t1 = time.perf_counter()
-    n_part, index_part = mk.partition(n, K, seed=a.seed, method=a.partition)                     # MK.R:15-41
-    beta0, bt = mk.start_values(d["y"], d["x"], 1.0, q, device=local)         # MK.R:53-55
-    p = d["x"].shape[1]
     vario, phi_kw = None, {}
-    if a.variogram is not None:               # every rank: the suggestion is a function of the data alone
-        vario = residual_variogram_before(mk, d, q, a, local, report=rank == 0)
-        if a.phi_from_variogram:
-            phi_kw = dict(phi_starting=vario["suggestion"]["starting"], phi_unif=vario["suggestion"]["unif"])
-    cfg = mk.SamplerConfig(q, p, beta0, bt, cov_model=c["cov"], n_batch=c["n_batch"], batch_length=c["batch_length"],
-                           seed=a.seed, predict_tile=c.get("predict_tile", 0), **phi_kw)
-    lo, hi = dmod.shard_range(K, world, rank)
-    subs = [mk.subset_data(d["y"], d["x"], 1.0, d["coords"], q, index_part[i]) for i in range(lo, hi)]
+    ses = None
+    if a.from_fit is None:
+        n_part, index_part = mk.partition(n, K, seed=a.seed, method=a.partition)                     # MK.R:15-41
+        beta0, bt = mk.start_values(d["y"], d["x"], 1.0, q, device=local)         # MK.R:53-55
+        p = d["x"].shape[1]
+        if a.variogram is not None:               # every rank: the suggestion is a function of the data alone
+            vario = residual_variogram_before(mk, d, q, a, local, report=rank == 0)
+            if a.phi_from_variogram:
+                phi_kw = dict(phi_starting=vario["suggestion"]["starting"], phi_unif=vario["suggestion"]["unif"])
+        # --save-fit: a tiled session (it keeps its chain states) whatever the config's tile
+        tile_cfg = c.get("predict_tile", 0) or (65536 if a.save_fit is not None else 0)
+        cfg = mk.SamplerConfig(q, p, beta0, bt, cov_model=c["cov"], n_batch=c["n_batch"], batch_length=c["batch_length"],
+                               seed=a.seed, predict_tile=tile_cfg, **phi_kw)
+        lo, hi = dmod.shard_range(K, world, rank)
+        subs = [mk.subset_data(d["y"], d["x"], 1.0, d["coords"], q, index_part[i]) for i in range(lo, hi)]
+    else:                                         # the chain of an earlier run: no partition, glm or MCMC
+        ses = mk.fitfile.load_session(os.path.join(a.from_fit, "session_0.npz"), device=local, predict_tile=a.predict_tile)
+        cfg = ses.cfg
+        if cfg.q != q:
+            raise SystemExit(f"--from-fit: the file's fit has q = {cfg.q}, --config {a.config} has q = {q}")
+        K, lo = ses.S, 0
+        c["K"], c["n_batch"], c["batch_length"] = K, cfg.n_batch, cfg.batch_length
+        subs = [None] * K                         # only their number is read below
+    kept_states = a.save_fit is not None or a.from_fit is not None    # the session takes its test sites after creation
     t["setup_s"] = time.perf_counter() - t1
 
     t2 = time.perf_counter()
     big = cfg.predict_tile > 0 and cfg.predict_tile < c["n_test"]
     C = q * c["n_test"]
     P = cfg.P
-    ses = None
     if subs:
         # one process, fused kriging: x.test goes in as MK.R:87 passes it, p.predict comes out
-        ses = mk.Session(subs, cfg, coords_test=d["coords_test"], subset_base=lo, device=local,
-                         x_test=d["x_test"] if ((world == 1 and not big) or need_p) else None,   # MK.R:108
-                         criteria=a.criteria)
+        x_test = d["x_test"] if ((world == 1 and not big) or need_p) else None   # MK.R:108
+        if not kept_states:
+            ses = mk.Session(subs, cfg, coords_test=d["coords_test"], subset_base=lo, device=local, x_test=x_test,
+                             criteria=a.criteria)
+        else:     # no test sites at creation: the session keeps every kept state; --criteria replays the recorded chain
+            if ses is None:
+                ses = mk.Session(subs, cfg, subset_base=lo, device=local, record_w=True)
+            ses.set_test_sites(d["coords_test"], x_test=x_test)
         if a.validate and world == 1:             # scored per subset: now (fused) or by the tile replays
             ses.set_validation(d["y_test"])
         if a.pair_thresholds is not None:         # filled now (fused) or by the tile replays
             ses.set_pairs(a.pair_thresholds)
-        for b in range(cfg.n_batch):          # progress every n.report = 10 batches (MK.R:84)
+        for b in range(cfg.n_batch if a.from_fit is None else 0):   # progress every n.report = 10 batches (MK.R:84)
             ses.run(cfg.batch_length)
             if rank == 0 and (b + 1) % 10 == 0:
                 print(f"batch {b + 1}/{cfg.n_batch}  {time.perf_counter() - t2:.1f}s", file=sys.stderr, flush=True)
+        if a.save_fit is not None:
+            os.makedirs(a.save_fit, exist_ok=True)
+            mk.fitfile.save_session(ses, os.path.join(a.save_fit, "session_0.npz"))
         t3 = time.perf_counter()
         # 1M sites (tiled kriging): the parameter grids now; w.predict tile by tile in the combine
         # one process: the grids to the host for the combine; N > 1: they stay in HBM (shard_grids below)
@@ -292,7 +330,7 @@ def main():
     t["end_to_end_s"] = time.perf_counter() - t1
     if rank == 0:
         rec = dict(config=a.config, workload=c, n_gpus=world, combine=a.combine, phases=t,
-                   subset_iters_per_s=K * cfg.n_samples / (t["fit_s"]) if world == 1 else None)
+                   subset_iters_per_s=K * cfg.n_samples / (t["fit_s"]) if world == 1 and a.from_fit is None else None)
         if summ is not None:
             truth = np.concatenate([d["beta_true"], [1.0] if q == 1 else [], [6.0] if q == 1 else []])
             rec["param_median"] = summ["param_quant"][0].tolist()
