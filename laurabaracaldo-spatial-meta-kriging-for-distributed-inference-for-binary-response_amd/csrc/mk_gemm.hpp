@@ -39,6 +39,7 @@
 //                  wave w owns blocks w and 7 - w of the triangular dimension, the dense chunks run
 //                  without a predicate and the triangular block's eight chunks are unrolled
 #pragma once
+#include <type_traits>
 #include "mk_common.hpp"
 
 namespace mk {
@@ -300,6 +301,119 @@ __device__ inline void acc_load_rw(AccRW<TM>& acc, const double* C, long ldc) {
     for (int bn = 0; bn < 8; ++bn)
 #pragma unroll
       for (int r = 0; r < 4; ++r) acc.v[bm][bn][r] = C[rw_row<TM>(bm) + (long)rw_col(bn, r) * ldc];
+}
+
+// ---------------------------------------------------------------- column strips: a ragged 128 x 128 row tile
+// A row tile of which only the first V < 8 16-row blocks hold valid rows (the last tile of a factor of
+// extent n_s + 1 inside n_pad).  In the row-wave form the waves that own padding rows idle, but the
+// waves that own valid rows still issue 16 MFMAs per k-step and the chunk barrier ties the workgroup
+// to them: the job is no shorter.  Here wave w owns the V valid row blocks of column blocks 2w and
+// 2w + 1 -- 2V MFMAs per k-step on every wave, V + 2 fragments -- and the padding row blocks are
+// neither loaded, multiplied nor stored.  Per element the MFMA sequence is mma_chunk_rw's (the same
+// chunks in the same order, four k-steps with k = 4 ks + (lane >> 4), first operand the column
+// block's fragment, second the row block's), so every valid element has the bits gemm_tile_rw gives
+// it; what changes is which wave holds which block.
+// Accumulator: lane l, register r of block (rb, j) is C[16 rb + (l & 15)][16 (2w + j) + (l >> 4) + 4r]:
+// a block's register image does not depend on the wave that holds it, so the strips go back to the
+// row-wave layout (cs_to_rw) as a copy of block images through LDS, no transpose.
+template <int V>
+using AccCS = AccT<V, 2>;
+constexpr int CS_VMAX = 6;   // strips where 2V <= 12; V = 7 (14 MFMAs and the relayout against 16) keeps the rows
+
+template <int V, bool NEG>
+__device__ inline void mma_chunk_cs(const double* As, const double* Bs, AccCS<V>& acc, int w) {
+  const int lane = threadIdx.x & 63;
+  const int li = lane & 15, lk = lane >> 4;
+#pragma unroll
+  for (int ks = 0; ks < GB_K / 4; ++ks) {
+    const int k = ks * 4 + lk;
+    double ya[V], xb[2];
+#pragma unroll
+    for (int b = 0; b < V; ++b) {
+      const double av = frag<true, 128>(As, b * 16 + li, k);
+      ya[b] = NEG ? -av : av;
+    }
+#pragma unroll
+    for (int j = 0; j < 2; ++j) xb[j] = frag<true, 128>(Bs, (2 * w + j) * 16 + li, k);
+#pragma unroll
+    for (int bm = 0; bm < V; ++bm)
+#pragma unroll
+      for (int j = 0; j < 2; ++j)
+        acc.v[bm][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(xb[j], ya[bm], acc.v[bm][j], 0, 0, 0);
+  }
+}
+
+// gemm_tile_rw<128, NEG> on the first V row blocks, K > 0.  w: the wave, wave-uniform.  The A image
+// still streams all 128 rows (one DMA instruction per k-row either way).  Ends with a barrier.
+template <int V, bool NEG>
+__device__ inline void gemm_tile_cs(const double* __restrict__ A, long sA, const double* __restrict__ B, long sB, int K,
+                                    AccCS<V>& acc, double* lds, int w) {
+  constexpr int STAGE = 2 * gb_img(128);
+  const int nch = K / GB_K;   // K > 0
+  auto issue = [&](int c) {
+    double* st = lds + (c & 1) * STAGE;
+    dma_chunk<true, 128>(A, sA, GB_K * c, st);
+    dma_chunk<true, 128>(B, sB, GB_K * c, st + gb_img(128));
+  };
+  issue(0);
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  for (int c = 0; c < nch; ++c) {
+    const double* st = lds + (c & 1) * STAGE;
+    if (c + 1 < nch) issue(c + 1);
+    mma_chunk_cs<V, NEG>(st, st + gb_img(128), acc, w);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+  }
+}
+
+template <int V>
+__device__ inline void acc_load_cs(AccCS<V>& acc, const double* C, long ldc, int w) {
+  const int li = threadIdx.x & 15, lk = (threadIdx.x & 63) >> 4;
+#pragma unroll
+  for (int bm = 0; bm < V; ++bm)
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) acc.v[bm][j][r] = C[16 * bm + li + (long)(16 * (2 * w + j) + lk + 4 * r) * ldc];
+}
+
+// The strips into the row-wave accumulator of the same tile: wave w' receives row blocks 2w' and
+// 2w' + 1 of all eight column blocks (zeros where the row block is padding: >= V).  Two rounds, one
+// per column block of a strip, each 4 waves x V block images of 2 KiB (lane-linear, 32 B per lane)
+// in the LDS the DMA stages have left: at most 56 KiB of gb_lds_bytes(128, 128).  The caller's last
+// barrier is behind it; ends with a barrier (the caller may reuse the LDS).
+template <int V>
+__device__ inline void cs_to_rw(const AccCS<V>& a, AccRW<128>& c, double* lds, int w) {
+  static_assert(V >= 1 && V <= 7 && 4 * V * 2048 <= gb_lds_bytes(128, 128), "a round fits the stages' LDS");
+  d2* img = (d2*)lds;   // block (rb, source wave ws): d2 index ((rb * 4 + ws) * 64 + lane) * 2
+  const int lane = threadIdx.x & 63;
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+#pragma unroll
+    for (int bm = 0; bm < V; ++bm) {
+      d2* p = img + ((bm * 4 + w) * 64 + lane) * 2;
+      p[0] = (d2){a.v[bm][j][0], a.v[bm][j][1]};
+      p[1] = (d2){a.v[bm][j][2], a.v[bm][j][3]};
+    }
+    __syncthreads();
+#pragma unroll
+    for (int bm = 0; bm < 2; ++bm) {
+      const int rb = 2 * w + bm;
+      if (rb < V) {   // wave-uniform
+#pragma unroll
+        for (int ws = 0; ws < 4; ++ws) {
+          const d2* p = img + ((rb * 4 + ws) * 64 + lane) * 2;
+          const d2 lo = p[0], hi = p[1];
+          c.v[bm][2 * ws + j] = (d4){lo[0], lo[1], hi[0], hi[1]};
+        }
+      } else {
+#pragma unroll
+        for (int ws = 0; ws < 4; ++ws) c.v[bm][2 * ws + j] = (d4){0.0, 0.0, 0.0, 0.0};
+      }
+    }
+    __syncthreads();
+  }
 }
 
 // The 128 x 128 form every kernel started from.

@@ -22,7 +22,7 @@ __global__ void k_chol_trsm(MatSet ms, int S, int h0, int hc, int k, int ia, int
 int pv_grid(int max_entries, int nt, int ntt);   // k_pred_var's grid (mk_linalg.hip)
 template <int TM>
 __global__ void k_chol_update_trsm(MatSet ms, int S, int h0, int hc, int k, int ia, int ib, int j0, int extra,
-                                   const int* slist, const int* scount, int syrk);
+                                   const int* slist, const int* scount, int syrk, const int* n_s, int ragged);
 __global__ void k_chol_diag(MatSet ms, const int* n_s, int h0, int hc, int k, double* ld_part, double* quad_c, int* info,
                             const int* slist, const int* scount, int cj0, int cj1, int syrk);
 __global__ void k_inv_copydiag(MatSet ms, const int* list, const int* count);

@@ -375,73 +375,21 @@ template __global__ void k_chol_trsm<128>(MatSet, int, int, int, int, int, int, 
 template __global__ void k_chol_trsm<64>(MatSet, int, int, int, int, int, int, const int*, const int*);
 template __global__ void k_chol_trsm<32>(MatSet, int, int, int, int, int, int, const int*, const int*);
 
-// Column k's update with the panel solve in its epilogue (k_chol_update_trsm):
-//   jobs t < ntk * 128/TM: rows of tile i = ia + t / (128/TM) (ia = k + 1, TM-row parts):
-//     C(i,k) -= sum_{j0 <= j < k} L(i,j) L(k,j)^T (k_chol_update's MFMA sequence, in the row-wave
-//     form: wave w holds TM/4 rows of all 128 columns; the accumulator starts from C in memory, so
-//     panels [0, j0) may have come from an earlier launch -- the split schedule's bulk stream), then
-//     L(i,k) = C(i,k) Winv_k^T straight from the accumulator (k_chol_trsm's sequence: chunks of 16
-//     in order from zero, the same fragment values) -- C(i,k) never goes through HBM between the
-//     two, and every wave solves its own rows: the same triangular work on all four SIMDs;
-//   job t = ntk * 128/TM (extra = 1, sequential schedule): the next diagonal tile's update by
-//     panels [0, k), stored partial (syrk: lower 16-blocks only, gemm_syrk_128 -- the tile's upper
-//     blocks in memory are not touched; syrk = 0: the full square); its correction by panel k
-//     (accumulator from memory) follows the launch, then its factor.
-// Winv_k exists before the launch starts.  Same per-element sequences as U(k), T(k): same bits
-// (tests/test_gpu_linalg.py).
-// Epilogue: the accumulator's block (bm, c), k-step r is chunk c's A fragment, in registers; the
-// output accumulates 32 columns at a time (the kernel stays within the 256 registers of two
-// workgroups per CU).
+// The solve epilogue of k_chol_update_trsm (below): L(i,k) = C(i,k) Winv_k^T from the row-wave
+// accumulator c, stored at C.  The accumulator's block (bm, ch), k-step r is chunk ch's A fragment, in
+// registers; the output accumulates 32 columns at a time (the kernel stays within the 256 registers
+// of two workgroups per CU).  nbm (wave-uniform): this wave's leading row blocks that hold valid rows
+// -- TM / 64 but in a ragged tile, whose padding row blocks are neither multiplied nor stored (a wave
+// with none still streams and waits with the others).  The caller's last barrier is behind it.
 template <int TM>
-__global__ __launch_bounds__(256, 2) void k_chol_update_trsm(MatSet ms, int S, int h0, int hc, int k, int ia, int ib,
-                                                            int j0, int extra, const int* slist, const int* scount,
-                                                            int syrk) {
-  extern __shared__ __attribute__((aligned(16))) double lds[];   // gb_lds_bytes(128, 128)
-  constexpr int SUB = MK_NB / TM, BM = TM / 64;
-  const int ntk = ib - ia;
-  int e, t, s, h;
-  // syrk: the extra jobs are 9/16 as long as the row jobs, and dealt among them (each matrix's last
-  // item) they made the launch slower, not faster -- a slot they free early takes the next row job
-  // beside a running one, and the launch ends with row jobs doubled up on some CUs while others idle
-  // (launches with an odd job count per matrix: 683 -> 787, 958 -> 1044 us).  Dealt after every row
-  // job of their XCD (xcd_map_tail) they fill the last wave instead (475 -> 400 us with two jobs per
-  // matrix, 821 -> 774 with four, 683 -> 673 with three; DESIGN.md 4.2).
-  const int E = active_pairs(slist, scount, S, hc);
-  if (!((extra && syrk) ? xcd_map_tail(E, ntk * SUB + extra, &e, &t) : xcd_map(E, ntk * SUB + extra, &e, &t)) ||
-      !pick_pair(slist, scount, e, h0, hc, &s, &h))
-    return;
-  const int sh = s * ms.q + h;
-  const int slot = 1 - ms.cur[sh];
-  double* M = mat_slot(ms, sh, slot);
-  const long ld = ms.ld;
-  if (t == ntk * SUB) {   // tile (ia, ia) of column ia, panels [0, k)
-    double* C = M + ia * MK_NB + (long)ia * MK_NB * ld;
-    if (syrk) {
-      AccSyrk a;
-      acc_load_syrk(a, C, ld);
-      gemm_syrk_128(M + ia * MK_NB, ld, k * MK_NB, a, lds);
-      store_tile_syrk(C, ld, a);
-      return;
-    }
-    Acc acc;
-    acc_load(acc, C, ld);
-    gemm_tile<128, 128, true, true, true>(M + ia * MK_NB, ld, M + ia * MK_NB, ld, k * MK_NB, k * MK_NB, acc, lds);
-    store_tile(C, ld, acc);
-    return;
-  }
-  const int i = ia + t / SUB, r0 = i * MK_NB + (t % SUB) * TM;
-  double* C = M + r0 + (long)k * MK_NB * ld;
-  AccRW<TM> c;
-  acc_load_rw<TM>(c, C, ld);
-  const long jo = (long)j0 * MK_NB * ld;
-  gemm_tile_rw<TM, true>(M + r0 + jo, ld, M + k * MK_NB + jo, ld, (k - j0) * MK_NB, c, lds);   // ends with a barrier
+__device__ inline void solve_epilogue_rw(const AccRW<TM>& c, int nbm, double* C, long ld, const double* Wt, double* lds) {
+  constexpr int BM = TM / 64;
   // opaque copies: the output addresses are computed here, not hoisted over the main loop beside
   // the accumulator (the compiler would otherwise keep acc_load's addresses live for the stores)
   double* Co = C;
   long ldo = ld;
   asm volatile("" : "+s"(Co), "+s"(ldo));
-  const double* Wt = winv_slot(ms, sh, slot, k);   // op(B)(j, n) = Wt[j * 128 + n]
-  asm volatile("" : "+s"(Wt));
+  asm volatile("" : "+s"(Wt));   // op(B)(j, n) = Wt[j * 128 + n]
   // four passes of 32 output columns, P = 3, 0, 2, 1 (pass P: n-blocks 2P, 2P+1, chunks 0 .. 2P+1);
   // each pass's 16 x 32 slices of Winv_k^T arrive by LDS-DMA while the previous pass multiplies
   // (buffers: passes 3, 2 at lds, passes 0, 1 behind pass 3's 48 KiB)
@@ -468,7 +416,7 @@ __global__ __launch_bounds__(256, 2) void k_chol_update_trsm(MatSet ms, int S, i
     acc_zero(o);
 #pragma unroll
     for (int ch = 0; ch < 8; ++ch) {
-      if (ch >= 2 * P + 2) break;
+      if (ch >= 2 * P + 2 || nbm == 0) break;   // nbm == 0: a wave of padding rows (it still streams and waits)
 #pragma unroll
       for (int ks = 0; ks < GB_K / 4; ++ks) {
         const int kk = ks * 4 + lk;
@@ -485,17 +433,126 @@ __global__ __launch_bounds__(256, 2) void k_chol_update_trsm(MatSet ms, int S, i
       }
     }
 #pragma unroll
-    for (int bm = 0; bm < BM; ++bm)
+    for (int bm = 0; bm < BM; ++bm) {
+      if (bm >= nbm) break;   // wave-uniform: a padding row block keeps its +0
 #pragma unroll
       for (int b = 0; b < 2; ++b)
 #pragma unroll
         for (int r = 0; r < 4; ++r) Co[rw_row<TM>(bm) + (long)rw_col(2 * P + b, r) * ldo] = o.v[bm][b][r];
+    }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
   }
 }
-template __global__ void k_chol_update_trsm<128>(MatSet, int, int, int, int, int, int, int, int, const int*, const int*, int);
-template __global__ void k_chol_update_trsm<64>(MatSet, int, int, int, int, int, int, int, int, const int*, const int*, int);
+
+// Column k's update with the panel solve in its epilogue (k_chol_update_trsm):
+//   jobs t < ntk * 128/TM: rows of tile i = ia + t / (128/TM) (ia = k + 1, TM-row parts):
+//     C(i,k) -= sum_{j0 <= j < k} L(i,j) L(k,j)^T (k_chol_update's MFMA sequence, in the row-wave
+//     form: wave w holds TM/4 rows of all 128 columns; the accumulator starts from C in memory, so
+//     panels [0, j0) may have come from an earlier launch -- the split schedule's bulk stream), then
+//     L(i,k) = C(i,k) Winv_k^T straight from the accumulator (k_chol_trsm's sequence: chunks of 16
+//     in order from zero, the same fragment values) -- C(i,k) never goes through HBM between the
+//     two, and every wave solves its own rows: the same triangular work on all four SIMDs;
+//     (TM = 128, ragged != 0) a row tile with at most CS_VMAX valid 16-row blocks runs the K loop in
+//     column strips and returns to the row-wave layout for the solve, see below;
+//   job t = ntk * 128/TM (extra = 1, sequential schedule): the next diagonal tile's update by
+//     panels [0, k), stored partial (syrk: lower 16-blocks only, gemm_syrk_128 -- the tile's upper
+//     blocks in memory are not touched; syrk = 0: the full square); its correction by panel k
+//     (accumulator from memory) follows the launch, then its factor.
+// Winv_k exists before the launch starts.  Same per-element sequences as U(k), T(k): same bits
+// (tests/test_gpu_linalg.py).
+// Epilogue: the accumulator's block (bm, c), k-step r is chunk c's A fragment, in registers; the
+// output accumulates 32 columns at a time (the kernel stays within the 256 registers of two
+// workgroups per CU).
+template <int TM>
+__global__ __launch_bounds__(256, 2) void k_chol_update_trsm(MatSet ms, int S, int h0, int hc, int k, int ia, int ib,
+                                                            int j0, int extra, const int* slist, const int* scount,
+                                                            int syrk, const int* __restrict__ n_s, int ragged) {
+  extern __shared__ __attribute__((aligned(16))) double lds[];   // gb_lds_bytes(128, 128)
+  constexpr int SUB = MK_NB / TM, BM = TM / 64;
+  const int ntk = ib - ia;
+  int e, t, s, h;
+  // syrk: the extra jobs are 9/16 as long as the row jobs, and dealt among them (each matrix's last
+  // item) they made the launch slower, not faster -- a slot they free early takes the next row job
+  // beside a running one, and the launch ends with row jobs doubled up on some CUs while others idle
+  // (launches with an odd job count per matrix: 683 -> 787, 958 -> 1044 us).  Dealt after every row
+  // job of their XCD (xcd_map_tail) they fill the last wave instead (475 -> 400 us with two jobs per
+  // matrix, 821 -> 774 with four, 683 -> 673 with three; DESIGN.md 4.2).
+  // ragged = 2: the last row tile's jobs are shorter too (the column strips below), so they go between
+  // the full row jobs and the extra jobs: longest first (xcd_map_tail2).
+  const int E = active_pairs(slist, scount, S, hc);
+  bool job;
+  if (TM == 128 && extra && syrk && ragged == 2 && ntk >= 2)
+    job = xcd_map_tail2(E, ntk + extra, &e, &t);
+  else if (extra && syrk)
+    job = xcd_map_tail(E, ntk * SUB + extra, &e, &t);
+  else
+    job = xcd_map(E, ntk * SUB + extra, &e, &t);
+  if (!job || !pick_pair(slist, scount, e, h0, hc, &s, &h)) return;
+  const int sh = s * ms.q + h;
+  const int slot = 1 - ms.cur[sh];
+  double* M = mat_slot(ms, sh, slot);
+  const long ld = ms.ld;
+  if (t == ntk * SUB) {   // tile (ia, ia) of column ia, panels [0, k)
+    double* C = M + ia * MK_NB + (long)ia * MK_NB * ld;
+    if (syrk) {
+      AccSyrk a;
+      acc_load_syrk(a, C, ld);
+      gemm_syrk_128(M + ia * MK_NB, ld, k * MK_NB, a, lds);
+      store_tile_syrk(C, ld, a);
+      return;
+    }
+    Acc acc;
+    acc_load(acc, C, ld);
+    gemm_tile<128, 128, true, true, true>(M + ia * MK_NB, ld, M + ia * MK_NB, ld, k * MK_NB, k * MK_NB, acc, lds);
+    store_tile(C, ld, acc);
+    return;
+  }
+  const int i = ia + t / SUB, r0 = i * MK_NB + (t % SUB) * TM;
+  double* C = M + r0 + (long)k * MK_NB * ld;
+  const long jo = (long)j0 * MK_NB * ld;
+  const double* Wt = winv_slot(ms, sh, slot, k);
+  // A ragged row tile (ragged != 0; TM = 128): v < 8 of its 16-row blocks hold rows of the factor's
+  // valid extent n_s + 1, the rest is padding, +0 from the assembly on.  With 2v <= 12 the K loop runs
+  // in column strips (gemm_tile_cs, mk_gemm.hpp: 2v MFMAs per wave and k-step instead of 16, the same
+  // sequence per element) and the strips return to the row-wave layout for the solve; the padding row
+  // blocks are not loaded, multiplied or stored.  Each v is a path of its own down to the kernel's end
+  // (an accumulator merged from several paths before a shared epilogue spills at the join).
+  if constexpr (TM == 128) {
+    const int v = ragged ? (n_s[s] + 1 - i * MK_NB + 15) >> 4 : 8;
+    if (v >= 1 && v <= CS_VMAX) {
+      const int w = syrk_wave();
+      auto run = [&](auto vt) {
+        constexpr int V = decltype(vt)::value;
+        AccRW<128> c;
+        {
+          AccCS<V> a;
+          acc_load_cs<V>(a, C, ld, w);
+          gemm_tile_cs<V, true>(M + r0 + jo, ld, M + k * MK_NB + jo, ld, (k - j0) * MK_NB, a, lds, w);
+          cs_to_rw<V>(a, c, lds, w);   // ends with a barrier
+        }
+        solve_epilogue_rw<128>(c, min(max(V - 2 * w, 0), 2), C, ld, Wt, lds);
+      };
+      switch (v) {
+        case 1: run(std::integral_constant<int, 1>{}); break;
+        case 2: run(std::integral_constant<int, 2>{}); break;
+        case 3: run(std::integral_constant<int, 3>{}); break;
+        case 4: run(std::integral_constant<int, 4>{}); break;
+        case 5: run(std::integral_constant<int, 5>{}); break;
+        default: run(std::integral_constant<int, 6>{}); break;
+      }
+      return;
+    }
+  }
+  AccRW<TM> c;
+  acc_load_rw<TM>(c, C, ld);
+  gemm_tile_rw<TM, true>(M + r0 + jo, ld, M + k * MK_NB + jo, ld, (k - j0) * MK_NB, c, lds);   // ends with a barrier
+  solve_epilogue_rw<TM>(c, BM, C, ld, Wt, lds);
+}
+template __global__ void k_chol_update_trsm<128>(MatSet, int, int, int, int, int, int, int, int, const int*, const int*, int,
+                                                 const int*, int);
+template __global__ void k_chol_update_trsm<64>(MatSet, int, int, int, int, int, int, int, int, const int*, const int*, int,
+                                                const int*, int);
 
 // ---------------------------------------------------------------- diagonal tile: factor + invert in LDS
 // 128x128 tile T (column-major, stride TLD) in LDS, 256 threads, blocked by 16 (see

@@ -150,6 +150,28 @@ static int inv_deal() {
   return on != 0;
 }
 
+// MK_RAGGED (default 1, read once per process): a 128-row job of the fused column update whose row
+// tile holds at most six valid 16-row blocks (the last tile of a factor of extent n_s + 1 < n_pad) runs
+// its K loop in column strips (gemm_tile_cs, mk_gemm.hpp) and leaves the padding row blocks alone, and
+// a launch whose last row tile is ragged in this way for its largest factor deals that tile's jobs
+// after the full row jobs and before the extra jobs: longest first (xcd_map_tail2).  0: the row-wave
+// body on all eight blocks, in the former order.  An argument of the kernel, so one build serves both
+// arms of an A/B; same bits on every valid element.
+static int ragged() {
+  static const int on = env_int("MK_RAGGED", 1);
+  return on != 0;
+}
+// The kernel's argument: 0 off, 1 the strips, 2 the strips and the order.  The order is per launch, so
+// it goes by the group's largest factor (n_pad is cut to the session's largest: its last tile is the
+// launch's last row tile); a smaller factor's ragged tile keeps its place among the full row jobs.
+static int ragged_arg(mk_session* s, const Group& g) {
+  if (!ragged()) return 0;
+  int nmax = 0;
+  for (int i = g.s0; i < g.s0 + g.S; ++i) nmax = std::max(nmax, (int)s->n_part[i]);
+  const int v = (nmax + 1 - (s->nt - 1) * MK_NB + 15) / 16;
+  return v >= 1 && v <= CS_VMAX ? 2 : 1;
+}
+
 // MK_INV_MAP (default 1, read once per process): the inverse levels' launches cut their tile jobs over
 // the XCDs by work and start the longest K ranges first (inv_map_job, mk_types.hpp); 0: xcd_map's cut
 // by item count in the matrices' item order, on its own grid.  An argument of the kernel, so one build
@@ -226,10 +248,10 @@ static void chol_update_trsm(mk_session* s, Group& g, hipStream_t st, int h0, in
   timed(s, st, tm == 128 ? KS_CHOL_UPDATE : KS_CHOL_UPDATE_SUB, flops, [&] {
     if (tm == 128)
       MK_LAUNCH(k_chol_update_trsm<128>, dim3(xcd_grid_h(E, nti + extra)), dim3(256), LDS_128, st, g.ms, g.S, h0, hc,
-                k, k + 1, nt, j0, extra, slist, scount, diag_syrk());
+                k, k + 1, nt, j0, extra, slist, scount, diag_syrk(), g.md.n_s, ragged_arg(s, g));
     else
       MK_LAUNCH(k_chol_update_trsm<64>, dim3(xcd_grid_h(E, 2 * nti + extra)), dim3(256), LDS_128, st, g.ms, g.S, h0,
-                hc, k, k + 1, nt, j0, extra, slist, scount, diag_syrk());
+                hc, k, k + 1, nt, j0, extra, slist, scount, diag_syrk(), g.md.n_s, 0);
   });
 }
 // cj0 < cj1: the diagonal tile's update by panels [cj0, cj1) first, in the same launch (fused form).

@@ -206,6 +206,28 @@ __device__ inline bool xcd_map_tail(int S, int T, int* s, int* t) {
   *t = T - 1;
   return true;
 }
+// Two tail classes (T >= 3): every entry's items t < T - 2 first, then the items T - 2 of all entries,
+// then the items T - 1.  Fits the same grid: ceil(S (T-2) / 8) + 2 ceil(S / 8) <= ceil(S / 8) T.
+__device__ inline bool xcd_map_tail2(int S, int T, int* s, int* t) {
+  const int x = blockIdx.x & 7;
+  int j = blockIdx.x >> 3;
+  const int Wr = S * (T - 2), Cr = (Wr + 7) >> 3, Cs = (S + 7) >> 3;
+  if (j < Cr) {
+    const int w = x * Cr + j;
+    if (w >= Wr) return false;
+    *s = w / (T - 2);
+    *t = w % (T - 2);
+    return true;
+  }
+  j -= Cr;
+  if (j >= 2 * Cs) return false;
+  const int cls = j >= Cs ? 1 : 0;
+  const int e = x * Cs + (j - cls * Cs);
+  if (e >= S) return false;
+  *s = e;
+  *t = T - 2 + cls;
+  return true;
+}
 __host__ inline int xcd_grid(int S, int T) { return 8 * ((S + 7) / 8) * T; }
 
 // ---------------------------------------------------------------- job map of the inverse levels
