@@ -357,6 +357,72 @@ int mk_meta_fit_ex(const mk_problem* prob, const mk_config* cfg, const int32_t* 
                    mk_progress_fn progress, void* user, mk_outputs* out, mk_combined* comb, mk_diagnostics* diag,
                    mk_criteria* crit);
 
+/* ---- leave-one-out: PSIS-LOO elpd and the Pareto shape k-hat per observation ----
+ * Pareto-smoothed importance-sampling leave-one-out (Vehtari, Gelman and Gabry 2017; R's loo): the
+ * criteria's pointwise likelihood matrix, smoothed importance weights, and per observation a shape
+ * estimate k-hat that says whether its term can be trusted (k-hat > 0.7: it cannot).
+ * Per subset, over the window's states k = 1..n and its observations i < n_s q (padding rows are
+ * masked).  The window is mk_session_set_kept_window's if set, else burn_in .. n.samples, every thin-th
+ * state from its first.  l_ik is exactly the criteria's term: crit_eta then loglik_term, the same
+ * operands in the same order, the binomial coefficient dropped.
+ * MK_LOO_MIN_STATES <= n <= MK_LOO_MAX_STATES, else MK_E_ARG naming n (above the cap: a larger thin);
+ * 25 is the smallest n with a tail of 5.
+ * For each observation, with r_k = -l_k - max_k(-l_k):
+ *   1. M = min(floor(n/5), ceil(3 sqrt(n))).  The tail is the M largest r; cut is the largest r not in
+ *      the tail.  Ties are broken by position in the sorted row: tied states have equal l, so no output
+ *      depends on it.
+ *   2. If the tail's largest value equals its smallest, nothing is smoothed and k-hat = +inf.
+ *   3. Otherwise the generalised-Pareto fit of Zhang and Stephens (2009) as loo applies it, with
+ *      x_j = exp(r_(j)) - exp(cut) over the tail in ascending order, j = 1..M:
+ *        G = 30 + floor(sqrt(M)),  x* = x_floor(M/4 + 0.5)
+ *        theta_g = 1/x_M + (1 - sqrt(G/(g - 1/2)))/(3 x*),  g = 1..G
+ *        k_g = (1/M) sum_j log1p(-theta_g x_j)
+ *        L_g = M (log(-theta_g/k_g) - k_g - 1)
+ *        omega_g = 1/sum_h exp(L_h - L_g)
+ *        theta = sum_g theta_g omega_g
+ *        k = (1/M) sum_j log1p(-theta x_j),  sigma = -k/theta
+ *        k-hat = (k M + 5)/(M + 10)
+ *   4. If k-hat is finite, the j-th smallest tail value is replaced by
+ *        min(log(sigma expm1(-k-hat log1p(-p_j))/k-hat + exp(cut)), 0),  p_j = (j - 1/2)/M;
+ *      if it is not, nothing is replaced.
+ *   5. lw_k = r_k - logsumexp(r);  elpd_loo_i = logsumexp_k(l_k + lw_k);
+ *      lppd_i = logsumexp_k(l_k) - log n.
+ * Relative efficiency is taken as 1: the chain's autocorrelation is not used to lengthen the tail.
+ * Rows per subset, N = n_s q:
+ *   elpd_loo     sum_i elpd_loo_i
+ *   p_loo        lppd - elpd_loo
+ *   looic        -2 elpd_loo
+ *   se_elpd_loo  sqrt(N var_i elpd_loo_i): two-pass variance, denominator N - 1, NaN when N = 1
+ *   lppd         sum_i lppd_i
+ *   k_max        the largest k-hat of the subset
+ *   n_k_bad      the count of k-hat > 0.7, as a double; +inf counts
+ *   lconst       as in the criteria
+ * pointwise per subset is (n_s q) x 3 column-major: elpd_loo_i, k-hat_i, lppd_i.  total: sums in subset
+ * order for elpd_loo, p_loo, looic, lppd, n_k_bad and lconst; the maximum for k_max; the root of the
+ * summed squares for se_elpd_loo.  A non-finite l in an observation's window makes its triple NaN and
+ * the subset's first seven rows NaN (the criteria's rule).
+ * Every sum runs in an order fixed by n, M and n_pad q alone (the row sorted; thread stride, then a
+ * fixed tree): two calls return the same bytes, and so do any two chunkings of the subsets. */
+#define MK_N_LOO 8               /* rows: elpd_loo, p_loo, looic, se_elpd_loo, lppd, k_max, n_k_bad, lconst */
+#define MK_LOO_MIN_STATES 25
+#define MK_LOO_MAX_STATES 8192   /* one observation's row is sorted in 64 KB of LDS */
+typedef struct mk_loo {          /* caller-allocated, any pointer may be NULL */
+  double* subsets;     /* [n_subsets] x 8                                                       */
+  double* total;       /* 8                                                                     */
+  double* pointwise;   /* [n_subsets] concatenated (n_s q) x 3 column-major                     */
+} mk_loo;
+/* After all iterations.  Always replays the recorded chain: that needs record_samples and record_w,
+ * else MK_E_ARG.  Window and thin are exactly mk_session_criteria's, including sessions without
+ * predict_tile that recorded both, and imported sessions.  The terms of a chunk of subsets are scratch
+ * (Np n doubles per subset, 1 GiB at a time; MK_LOO_CHUNK=<subsets> overrides), freed on return; a
+ * chunk that does not fit is MK_E_NOMEM.  Nothing is launched or allocated unless this is called. */
+int mk_session_loo(mk_session* s, int32_t thin, mk_loo* out);
+/* The same kernel on a caller's log-likelihood matrix on the host: ell is n_states x n_obs column-major,
+ * one observation per column.  pointwise (n_obs x 3 column-major) and row (8, lconst 0) may be NULL.
+ * Columns are uploaded in chunks (bounded in bytes; MK_LOO_CHUNK=<columns> overrides); the triples of
+ * all columns stay in one device buffer and the row is reduced once, so nothing depends on the chunk. */
+int mk_loo_matrix(const double* ell, int64_t n_obs, int32_t n_states, double* pointwise, double* row, int32_t device);
+
 /* ---- held-out validation: log score, Brier score and error rate at the test sites ----
  * The out-of-sample companion of the model assessment above.  Held-out data are y_test and wt_test,
  * q*n_test each, location-major like x_test: y successes of wt trials; a column with wt = 0 is "not

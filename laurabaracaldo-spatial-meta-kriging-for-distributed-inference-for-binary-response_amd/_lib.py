@@ -27,6 +27,9 @@ N_LEVELS = 200
 N_DIAG = 3             # MK_N_DIAG: rows ess, mcse, rhat
 N_CRIT = 8             # MK_N_CRIT: the rows of mk_criteria, in CRIT_NAMES' order
 CRIT_NAMES = ["bar.D", "D.bar.Omega", "pD", "DIC", "lppd", "p.waic", "WAIC", "lconst"]
+N_LOO = 8              # MK_N_LOO: the rows of mk_loo, in LOO_NAMES' order
+LOO_NAMES = ["elpd_loo", "p_loo", "looic", "se_elpd_loo", "lppd", "k_max", "n_k_bad", "lconst"]
+LOO_MIN_STATES, LOO_MAX_STATES = 25, 8192      # MK_LOO_MIN_STATES, MK_LOO_MAX_STATES
 N_SCORE = 5            # MK_N_SCORE: the rows of mk_scores, in SCORE_NAMES' order
 SCORE_NAMES = ["n", "lpd", "brier", "err", "lconst"]
 MAP_MAXT = 8           # MK_MAP_MAXT: exceedance thresholds at most
@@ -93,6 +96,10 @@ class Diagnostics(ctypes.Structure):
 
 
 class Criteria(ctypes.Structure):
+    _fields_ = [("subsets", _dp), ("total", _dp), ("pointwise", _dp)]
+
+
+class Loo(ctypes.Structure):
     _fields_ = [("subsets", _dp), ("total", _dp), ("pointwise", _dp)]
 
 
@@ -172,6 +179,8 @@ EXPORTS = {
     "mk_score_grid": (ctypes.c_int, [_dp, ctypes.c_int32, ctypes.c_int64, _dp, _dp, _dp, _dp, ctypes.c_int32]),
     "mk_session_set_criteria": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32]),
     "mk_session_criteria": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(Criteria)]),
+    "mk_session_loo": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(Loo)]),
+    "mk_loo_matrix": (ctypes.c_int, [_dp, ctypes.c_int64, ctypes.c_int32, _dp, _dp, ctypes.c_int32]),
     "mk_meta_fit": (ctypes.c_int, [ctypes.POINTER(Problem), ctypes.POINTER(Config), _ip, ctypes.c_int32,
                                    PROGRESS_FN, ctypes.c_void_p, ctypes.POINTER(Outputs), ctypes.POINTER(Combined)]),
     "mk_meta_fit_diag": (ctypes.c_int, [ctypes.POINTER(Problem), ctypes.POINTER(Config), _ip, ctypes.c_int32,

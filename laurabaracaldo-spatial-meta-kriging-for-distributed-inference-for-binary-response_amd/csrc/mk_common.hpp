@@ -119,6 +119,14 @@ __device__ inline double pred_prob(const double* __restrict__ xrow, long ldx, co
   return pred_linkinv(pred_eta(xrow, ldx, beta, p, w), link);
 }
 
+// eta of observation i of a fitted subset (the criteria, mk_criteria.hip, and PSIS-LOO, mk_loo.hip): column j
+// of the subset's design at x + j * Np (pred_prob's accumulation).
+__device__ inline double crit_eta(const double* __restrict__ x, long Np, const double* __restrict__ beta, int p, double w) {
+  double acc = 0.0;
+  for (int j = 0; j < p; ++j) acc = fma(x[(long)j * Np], beta[j], acc);
+  return acc + w;
+}
+
 // spBayes util logitInv(z, a, b) = b - (b-a)/(1+exp(z))
 __device__ __host__ inline double logit_inv(double z, double a, double b) { return b - (b - a) / (1.0 + exp(z)); }
 __device__ inline double unif_jacobian(double v, double a, double b) { return log(v - a) + log(b - v); }

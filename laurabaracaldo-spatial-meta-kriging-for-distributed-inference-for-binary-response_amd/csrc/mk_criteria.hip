@@ -54,13 +54,6 @@ __device__ inline void crit_update(CritState& st, double l, int k) {
 // A running sum's state k: the first state sets it.
 __device__ inline double crit_add(double cur, double v, int k) { return k == 0 ? v : cur + v; }
 
-// eta of observation i: column j of the subset's design at x + j * Np (pred_prob's accumulation).
-__device__ inline double crit_eta(const double* __restrict__ x, long Np, const double* __restrict__ beta, int p, double w) {
-  double acc = 0.0;
-  for (int j = 0; j < p; ++j) acc = fma(x[(long)j * Np], beta[j], acc);
-  return acc + w;
-}
-
 // Kept iteration kidx (0-based): grid (nb, S).
 __global__ __launch_bounds__(256) void k_crit_accum(Model md, Crit c, int kidx) {
   __shared__ double red[8];

@@ -8,6 +8,7 @@
 //   mk_parity.hip    parity-test entry points
 //   mk_diag.hip      chain diagnostics: the launcher, the session entry points, the tile sink
 //   mk_criteria.hip  model assessment (DIC, WAIC): the kernels, the scratch, the session entry points
+//   mk_loo.hip       leave-one-out (PSIS-LOO elpd and k-hat per observation): the kernels, the entry points
 //   mk_scores.hip    held-out validation (log score, Brier, error rate): the kernels, the entry points
 //   mk_maps.hip      posterior maps (mean, sd, exceedance of p(y = 1)): the kernel, the entry points
 //   mk_pairs.hip     cross-outcome prediction (co-occurrence and contrast of two outcomes): the kernels, the entry points
@@ -81,7 +82,7 @@ static inline double matern_span_pt(const double* b, const double* t) {
                     std::fmax(std::fabs(b[3] - t[2]), std::fabs(t[3] - b[2])));
 }
 
-constexpr int NKSTAT = 20;
+constexpr int NKSTAT = 21;
 // KS_CHOL_UPDATE: the 128-tile panel-update launches (k_chol_update<128>); KS_CHOL_UPDATE_SUB:
 // the 64- / 32-sub-tile ones (small grids).  Together: the roofline kernel k_chol_update.
 // KS_UPDATE_BUSY: both, with the time of launches that overlap (the split schedule's bulk and
@@ -91,7 +92,7 @@ constexpr int NKSTAT = 20;
 // KS_COV: the candidates' covariance assembly (k_cov_candidate, with k_matern_table for Matern).
 enum { KS_CHOL_UPDATE = 0, KS_CHOL_DIAG, KS_CHOL_TRSM, KS_SWEEP, KS_LAUUM, KS_ITER, KS_INV, KS_CHOL_UPDATE_SUB,
        KS_UPDATE_BUSY, KS_PRED_VAR, KS_COV, KS_SWEEP_FALLBACK, KS_KRIG_CHEB, KS_KRIG_FALLBACK, KS_DIAG, KS_CRIT,
-       KS_SCORE, KS_MAPS, KS_PAIRS, KS_REGIONS };
+       KS_SCORE, KS_MAPS, KS_PAIRS, KS_REGIONS, KS_LOO };
 // KS_KRIG_CHEB: tiles kriged by phi interpolation (predict_tile_cheb): launches = tiles, flops = exact
 // s evaluations (one per (subset, outcome) pair and node or check point), total_ms = the largest check
 // difference seen over all pairs and sites (not a time).  KS_KRIG_FALLBACK: tiles whose check failed
@@ -115,6 +116,9 @@ enum { KS_CHOL_UPDATE = 0, KS_CHOL_DIAG, KS_CHOL_TRSM, KS_SWEEP, KS_LAUUM, KS_IT
 // k_region_cov_node per node and check slot, k_region_check, and k_region_interp_factor and k_region_draw per
 // chunk of kept states in their place; launches counts kernels), bracketed by events whether or not the
 // profiler is on; none are made unless regions were attached.
+// KS_LOO: the PSIS-LOO launches (k_loo_terms and k_loo_psis per chunk of subsets, k_loo_finish and k_loo_total
+// per mk_session_loo), bracketed by events whether or not the profiler is on; none are made unless
+// mk_session_loo is called.
 // KS_SWEEP_FALLBACK: launches = (subset, iteration) sweeps k_sweep_mg refused admission and its
 // k_sweep fallback ran (counted on the device, read at the end of every mk_session_run; no timing).
 

@@ -2,9 +2,9 @@
 caller's layouts: one table of field -> shape serves Session.outputs and meta_fit_node."""
 import numpy as np
 
-from ._lib import (CRIT_NAMES, MAP_BASE_NAMES, N_CRIT, N_DIAG, N_LEVELS, N_MAP_BASE, N_PAIR_BASE, N_SCORE,
-                   PAIR_BASE_NAMES, REGION_BASE_NAMES, SCORE_NAMES, Criteria, Diagnostics, MapSpec, Maps, Outputs, PairSpec,
-                   Pairs, Regions, RegionSpec, Scores, Validation, dptr, iptr)
+from ._lib import (CRIT_NAMES, LOO_NAMES, MAP_BASE_NAMES, N_CRIT, N_DIAG, N_LEVELS, N_LOO, N_MAP_BASE, N_PAIR_BASE, N_SCORE,
+                   PAIR_BASE_NAMES, REGION_BASE_NAMES, SCORE_NAMES, Criteria, Diagnostics, Loo, MapSpec, Maps, Outputs,
+                   PairSpec, Pairs, Regions, RegionSpec, Scores, Validation, dptr, iptr)
 
 # The array libmk fills for each mk_outputs field, row-major, in terms of: K subsets, P parameters,
 # C = q n_test kriging columns, L levels, n = n_samples, kept states, B amcmc batches, R = P + 1
@@ -114,6 +114,29 @@ class CriteriaBuffers:
             for N in self.n_obs:                              # column-major (n_s q) x 2 per subset
                 out["pointwise"].append(self.pointwise[off:off + 2 * N].reshape(2, N).T.copy())
                 off += 2 * N
+        return out
+
+
+class LooBuffers:
+    """The arrays behind an mk_loo of K subsets (n_part sites each, q outcomes): `.c` points at them;
+    unpack() gives {'subsets': (K, 8), 'total': (8,), 'names': the rows' names} and, with pointwise,
+    'pointwise': per subset an (n_s q) x 3 array, columns elpd_loo_i, k-hat_i and lppd_i."""
+
+    def __init__(self, K, q, n_part, pointwise=False):
+        self.n_obs = [int(ns) * int(q) for ns in n_part]
+        self.subsets = np.zeros((int(K), N_LOO))
+        self.total = np.zeros(N_LOO)
+        self.pointwise = np.zeros(3 * sum(self.n_obs)) if pointwise else None
+        self.c = Loo()
+        self.c.subsets, self.c.total, self.c.pointwise = dptr(self.subsets), dptr(self.total), dptr(self.pointwise)
+
+    def unpack(self):
+        out = {"subsets": self.subsets.copy(), "total": self.total.copy(), "names": list(LOO_NAMES)}
+        if self.pointwise is not None:
+            out["pointwise"], off = [], 0
+            for N in self.n_obs:                              # column-major (n_s q) x 3 per subset
+                out["pointwise"].append(self.pointwise[off:off + 3 * N].reshape(3, N).T.copy())
+                off += 3 * N
         return out
 
 

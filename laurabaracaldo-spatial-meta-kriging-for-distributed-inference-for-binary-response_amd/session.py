@@ -10,8 +10,8 @@ import numpy as np
 
 from . import _lib
 from ._lib import Config, Problem, check, dptr, iptr
-from .outbuf import (CriteriaBuffers, DiagnosticBuffers, MapBuffers, OutputBuffers, PairBuffers, RegionBuffers, ScoreBuffers,
-                     map_names, map_spec, pair_spec, region_spec, validation_arrays)
+from .outbuf import (CriteriaBuffers, DiagnosticBuffers, LooBuffers, MapBuffers, OutputBuffers, PairBuffers, RegionBuffers,
+                     ScoreBuffers, map_names, map_spec, pair_spec, region_spec, validation_arrays)
 
 COV_MODELS = {"exponential": _lib.MK_COV_EXPONENTIAL, "matern": _lib.MK_COV_MATERN}
 LINKS = {"logit": _lib.MK_LINK_LOGIT, "probit": _lib.MK_LINK_PROBIT}
@@ -25,6 +25,7 @@ KS_SCORE = 16     # the held-out scoring launches (always timed; 0 launches unle
 KS_MAPS = 17      # the posterior-map launches (always timed; 0 launches unless maps were asked for)
 KS_PAIRS = 18     # the cross-outcome launches (always timed; 0 launches unless pairs were asked for)
 KS_REGIONS = 19   # the areal-prediction launches (always timed; 0 launches unless regions were attached)
+KS_LOO = 20       # the PSIS-LOO launches (always timed; 0 launches unless loo() was called)
 
 
 def _f64(a):
@@ -361,6 +362,16 @@ class Session:
         check(self._lib.mk_session_criteria(self._h, int(thin), ctypes.byref(cb.c)))
         return cb.unpack()
 
+    def loo(self, thin=1, pointwise=False):
+        """PSIS-LOO per subset after the run (mk_session_loo; the definitions are in include/mk.h):
+        {'subsets': (S, 8), 'total': (8,), 'names': the rows -- elpd_loo, p_loo, looic, se_elpd_loo, lppd,
+        k_max, n_k_bad, lconst}; pointwise=True adds 'pointwise', per subset (n_s q) x 3: elpd_loo_i, the
+        Pareto shape k-hat_i (above 0.7 the term is not reliable) and lppd_i.  Always replays the recorded
+        chain (record_w) over criteria()'s window and thin: 25 .. 8192 states."""
+        lb = LooBuffers(self.S, self.q, self.n_part, pointwise=pointwise)
+        check(self._lib.mk_session_loo(self._h, int(thin), ctypes.byref(lb.c)))
+        return lb.unpack()
+
     def set_validation(self, y_test, weights_test=1):
         """Attach held-out outcomes at the current test sites (mk_session_set_validation): y_test
         (q*n_test, location-major like x_test) successes of weights_test trials (1: binary; 0 marks a
@@ -629,6 +640,44 @@ def score_grid(p, y, weights=1, pointwise=False, device=0):
     if pointwise:
         out["pointwise"] = pw.T.copy()
     return out
+
+
+def psis_loo(ell, pointwise=True, device=0):
+    """PSIS-LOO of a matrix of log-likelihood terms on the device (mk_loo_matrix; the kernel the sessions
+    use): ell is n_states x n_obs, its rows equally weighted states -- a chain from other software, say.
+    Returns the row by name (elpd_loo, p_loo, looic, se_elpd_loo, lppd, k_max, n_k_bad, lconst = 0) and,
+    with pointwise, 'pointwise' (n_obs x 3: elpd_loo_i, k-hat_i, lppd_i).  25 .. 8192 states."""
+    lib = _lib.load()
+    e = np.asarray(ell, dtype=np.float64)
+    if e.ndim != 2:
+        raise ValueError("error: psis_loo takes a 2-d array (states x observations)")
+    n, N = e.shape
+    cols = _f64(e.T)                                          # one contiguous row of states per observation
+    pw = np.zeros((3, N)) if pointwise else None
+    row = np.zeros(_lib.N_LOO)
+    check(lib.mk_loo_matrix(dptr(cols), int(N), int(n), dptr(pw), dptr(row), int(device)))
+    out = dict(zip(_lib.LOO_NAMES, row.tolist()))
+    if pointwise:
+        out["pointwise"] = pw.T.copy()
+    return out
+
+
+def loo_compare(a, b):
+    """Two PSIS-LOO results with pointwise values over the same observations (Session.loo(pointwise=True),
+    spLoo, psis_loo): {'elpd_diff': sum_i (a_i - b_i), 'se_diff': sqrt(N var_i (a_i - b_i)) with the N - 1
+    denominator, 'n_k_bad': observations whose k-hat exceeds 0.7 in either fit}.  Positive favours a."""
+    def pw(r):
+        if not isinstance(r, dict) or "pointwise" not in r:
+            raise ValueError("error: loo_compare needs results with pointwise values (pointwise=True)")
+        p = r["pointwise"]
+        return np.concatenate(p, axis=0) if isinstance(p, (list, tuple)) else np.asarray(p)
+    pa, pb = pw(a), pw(b)
+    if pa.shape != pb.shape or pa.ndim != 2 or pa.shape[1] != 3:
+        raise ValueError(f"error: loo_compare needs the same observations in both fits, not {pa.shape} and {pb.shape}")
+    d = pa[:, 0] - pb[:, 0]
+    N = d.size
+    se = float(np.sqrt(N * np.sum((d - d.mean()) ** 2) / (N - 1))) if N > 1 else float("nan")
+    return {"elpd_diff": float(d.sum()), "se_diff": se, "n_k_bad": int(np.sum((pa[:, 1] > 0.7) | (pb[:, 1] > 0.7)))}
 
 
 def map_grid(grid, thresholds=(), device=0):

@@ -138,7 +138,7 @@ def spMvGLM(formula, coords, weights, starting, tuning, priors, amcmc, cov_model
 
 def load_fit(path, device=0):
     """The spMvGLM fit SpMvGLMFit.save wrote, on `device`: the same keys, and a session rebuilt from the file's
-    chain (fitfile.load_session), so spPredict, spDiag, spDiagnostics, spValidate, spMaps, spPairs and spRegions
+    chain (fitfile.load_session), so spPredict, spDiag, spLoo, spDiagnostics, spValidate, spMaps, spPairs and spRegions
     serve it unchanged.  p.beta.theta.samples and p.w.samples are the saved bytes; the kriging draws agree with
     the original fit's to rounding (the record's z is recomputed from w)."""
     a = fitfile.read(path)
@@ -192,6 +192,29 @@ def spDiag(sp_obj, start=1, end=None, thin=1):
     c = ses.criteria(thin=thin)
     row = dict(zip(c["names"], c["subsets"][0].tolist()))
     return {"DIC": {k: row[k] for k in c["names"][:4]}, "WAIC": {k: row[k] for k in c["names"][4:]}}
+
+
+def spLoo(sp_obj, start=1, end=None, thin=1):
+    """PSIS-LOO of an spMvGLM fit (R's loo on the fit's pointwise likelihood), on the device: the rows by name
+    -- "elpd_loo", "p_loo", "looic", "se_elpd_loo", "lppd", "k_max", "n_k_bad", "lconst" -- over iterations
+    start..end (1-based, inclusive), every thin-th, replayed from the chain the fit recorded, plus "pointwise"
+    ((n q) x 3: elpd_loo_i, the Pareto shape k-hat_i, lppd_i).  25 .. 8192 states.  The definitions are in
+    include/mk.h; two results go to loo_compare."""
+    ses = sp_obj.get("_session")
+    if ses is None:
+        raise ValueError("error: the spMvGLM fit was closed; spLoo needs its recorded chain")
+    n_samples = sp_obj["_n_samples"]
+    end = n_samples if end is None else int(end)
+    start, thin = int(start), int(thin)
+    if not (1 <= start <= end <= n_samples):
+        raise ValueError("error: invalid start/end")
+    if thin < 1:
+        raise ValueError("error: invalid thin")
+    ses.set_kept_window(start, end)
+    r = ses.loo(thin=thin, pointwise=True)
+    res = dict(zip(r["names"], r["subsets"][0].tolist()))
+    res["pointwise"] = r["pointwise"][0]
+    return res
 
 
 def spValidate(sp_obj, pred_coords, pred_covars, y, weights=1, start=1, end=None):

@@ -68,6 +68,10 @@ def main():
                     help="model assessment (DIC and WAIC, accumulated on the device over the kept iterations): one "
                          "more JSON line, {\"criteria\": the rows summed over the subsets}; one process (plain or "
                          "--devices)")
+    ap.add_argument("--loo", action="store_true",
+                    help="PSIS-LOO (leave-one-out elpd and the Pareto shape k-hat per observation, on the device, "
+                         "replayed from the recorded chain over the kept iterations): one more JSON line, {\"loo\": "
+                         "the total row by name}; one process, plain path")
     ap.add_argument("--validate", action="store_true",
                     help="held-out validation against y.test (log score, Brier score, error rate on the device): "
                          "one more JSON line, {\"validation\": the combined p grid's row, the median subset's row, "
@@ -131,6 +135,8 @@ def main():
             ap.error("--save-fit and --from-fit run in the plain path (one process), not with --devices")
         if a.variogram is not None:
             ap.error("--variogram and --phi-from-variogram run in the plain path (one process per GPU), not with --devices")
+        if a.loo:
+            ap.error("--loo runs in the plain path (one process), not with --devices")
         return node_main(a, c)
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -138,6 +144,8 @@ def main():
         ap.error("--diagnostics runs in one process: plain, or over several GPUs with --devices")
     if a.criteria and world > 1:
         ap.error("--criteria runs in one process: plain, or over several GPUs with --devices")
+    if a.loo and world > 1:
+        ap.error("--loo runs in one process")
     if a.pair_thresholds is not None and world > 1:
         ap.error("--pairs runs in one process: plain, or over several GPUs with --devices")
     if (a.save_fit is not None or a.from_fit is not None) and world > 1:
@@ -198,7 +206,7 @@ def main():
         x_test = d["x_test"] if ((world == 1 and not big) or need_p) else None   # MK.R:108
         if not kept_states:
             ses = mk.Session(subs, cfg, coords_test=d["coords_test"], subset_base=lo, device=local, x_test=x_test,
-                             criteria=a.criteria)
+                             criteria=a.criteria, record_w=a.loo)     # --loo replays the recorded chain
         else:     # no test sites at creation: the session keeps every kept state; --criteria replays the recorded chain
             if ses is None:
                 ses = mk.Session(subs, cfg, subset_base=lo, device=local, record_w=True)
@@ -223,6 +231,7 @@ def main():
                if world == 1
                else {"parameters": [], "w_predict": []})
         crit = ses.criteria() if a.criteria else None
+        loo = ses.loo() if a.loo else None
         scores = ses.scores() if (a.validate and world == 1 and not big) else None
     else:                                         # K < world: this rank has no subsets, it joins the exchange
         t3 = time.perf_counter()
@@ -346,6 +355,8 @@ def main():
             print(json.dumps({"diagnostics": mk.convergence_report(diag)}), flush=True)
         if a.criteria:
             print(json.dumps({"criteria": dict(zip(crit["names"], crit["total"].tolist()))}), flush=True)
+        if a.loo:
+            print(json.dumps({"loo": dict(zip(loo["names"], loo["total"].tolist()))}), flush=True)
         if vario is not None:
             print(json.dumps({"variogram": vario["line"]}), flush=True)
         if a.validate and result3 is not None:
