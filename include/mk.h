@@ -205,7 +205,10 @@ int mk_session_tile_grids_wp(mk_session* s, int32_t t0, double* out_w, double* o
  * kernel) and ms, always timed, 0 launches unless pairs were asked for; 19 the areal-prediction launches
  * k_region_cov / k_region_draw per kept state and k_quantiles / k_map_cols per replay (on the interpolated
  * route the node covariances, the check and two launches per chunk of kept states) -- launches (one per
- * kernel) and ms, always timed, 0 launches unless regions were attached).  Flops are algorithmic, not executed: GEMM tiles 2 m n k, the diagonal tile's
+ * kernel) and ms, always timed, 0 launches unless regions were attached; 20 the
+ * PSIS-LOO launches -- always timed, 0 launches unless mk_session_loo is called; 21 the state-digest launches
+ * k_state_digest / k_digest_reduce of a checkpoint, a restore or mk_session_digest -- launches and ms, always
+ * timed, 0 launches unless one of those calls is made).  Flops are algorithmic, not executed: GEMM tiles 2 m n k, the diagonal tile's
  * update as a SYRK, solves and inverse products over their triangles.  mk_session_profile(s, enable)
  * before mk_session_run: enable 0 = off, 1 = every kind, otherwise a mask with bit (1 + kind) per kind
  * bracketed (e.g. 2 << 0 = the panel update only; fewer events, less overhead). */
@@ -917,6 +920,91 @@ int32_t mk_session_imported(const mk_session* s);          /* 1 after a successf
  * Cholesky, inverse) and of the z = W u launches (k_import_z), by device events.  Any pointer may be NULL;
  * MK_E_ARG unless the session was imported. */
 int mk_session_import_stats(const mk_session* s, int64_t* factorisations, double* ms_factor, double* ms_z);
+
+/* ---- checkpoints: continue a chain in a later process ----
+ * The chain is deterministic given its state (the Philox streams are keyed by seed, global subset and iteration
+ * and carry none), so a chain stopped after any iteration, written out, read by a fresh process and continued
+ * reports the bytes of the chain that never stopped.  mk_session_checkpoint copies that state to the host,
+ * mk_session_restore puts it into a session made over the same data and configuration.
+ *
+ * The state is MK_CKPT_NFIELDS fields of 8-byte words (doubles but for notpd, int64), each [count] x words[f],
+ * subset-major, in the session's padded device layout (n_pad = the largest subset + 1 rounded up to 128,
+ * Np = n_pad q, nmh = p + n_theta + Np), as raw bytes:
+ *    0 beta [p]           1 theta [n_theta]     2 w [Np]             3 eta [Np] (padding zeroed)
+ *    4 tune [nmh]         5 acc [nmh]           6 u [q n_pad]        7 z [q n_pad]
+ *    8 Z [q q n_pad]      9 logdetR [q]        10 quad [q]          11 A_full [q q]
+ *   12 Ainv [q q]        13 notpd [q] int64
+ *   14 crit_acc [6 Np]   15 crit_part [k nb]   16 crit_sbeta [p]    in-chain criteria (else 0 words; 14 and
+ *                                                                   16 once a kept iteration ran; padding zeroed)
+ *   17 samples [it P]    18 w_samples [it Np] (record_w)            19 acc_hist [it / batch.length][P + 1]
+ *   20 kz [k q n_pad]    21 kth [k n_theta]    22 kA [k q q]        a tiled session's kept-state record
+ *   23 w_pred [k q n_test]                                          a fused session's kriging draws
+ * with it the iterations done and k = max(0, it - burn_in + 1) the kept ones: only the rows that exist are
+ * moved.  mk_session_checkpoint_layout writes the words per subset of every field at `iteration` (-1: the
+ * iterations done so far) into words[MK_CKPT_NFIELDS]; the caller allocates count x words[f] x 8 bytes per field
+ * and count q MK_CKPT_NDIGEST uint64 for the digests.
+ *
+ * The factors (L, Winv, W, QB of the accepted slots) and a fused session's kriging buffers are not part of the
+ * state: the restore re-derives them from the restored theta with the session's own candidate, Cholesky and
+ * inverse kernels, then refreshes the kriging buffers of every pair.  The carried schedule state (queued
+ * lookahead candidates, the early assembly, pending table draws) is dropped; the schedules re-prime themselves.
+ * So that "re-derived, hence the same bits" is checked and not assumed, a checkpoint carries per (subset,
+ * outcome) pair a 64-bit digest of each factor buffer over the region later iterations read -- columns and rows
+ * below n_s; the bordered row and scratch are outside -- and the restore compares the digests of what it
+ * re-derived: a mismatch is MK_E_HIP naming the pair and the buffer, and the session is left poisoned.
+ *
+ * The digest of words x_0 .. x_{m-1} (a double's bit pattern) is
+ *    D = sum_i mix(x_i + (i + 1) * 0x9E3779B97F4A7C15) mod 2^64,
+ * mix the splitmix64 finaliser (x ^= x >> 30, x *= 0xBF58476D1CE4E5B9, x ^= x >> 27, x *= 0x94D049BB133111EB,
+ * x ^= x >> 31).  The regions' enumeration: MK_DIGEST_L and MK_DIGEST_W the lower triangle of the leading n_s x
+ * n_s block, column-major (column c: rows c .. n_s - 1); MK_DIGEST_WINV per 128-tile k, m_k = min(128, n_s -
+ * 128 k) > 0, the lower triangle of its leading m_k x m_k block, column-major, tile after tile; MK_DIGEST_QB per
+ * tile its two diagonal 64 x 64 quadrants (the sweeps read, and the library computes, no other part of a tile),
+ * of each the leading block below n_s, column-major, quadrant 0 then 1 (0 for a session whose sweep keeps no QB).
+ *
+ * mk_session_checkpoint: subsets [first, first + count); MK_E_ARG on an imported session (it holds no sampler
+ * state; the fit file is the tool there) or a poisoned one.  mk_session_restore: the session must be as
+ * mk_session_create left it (no iteration run, nothing imported, not poisoned); `words` are the caller's sizes
+ * per subset of every field, and all the session's subsets are restored -- a subset range of a checkpoint goes
+ * into a session made over those subsets with subset_base moved by `first`, which must have the same n_pad.
+ * Refused on the host before any device work (MK_E_ARG, naming subset, field, expected and given size):
+ * iteration outside 0 .. n.samples, a size that differs from the layout, a missing field, a non-finite theta,
+ * tune or w, an accept count that is negative or not integral.  A restored theta whose R(phi, nu) meets a pivot
+ * that is not > 0 is MK_E_ARG naming the pair, and the session is left as created.  Afterwards
+ * mk_session_iteration returns `iteration`, mk_session_run continues the chain, and once iteration = n.samples
+ * every output and sink behaves as on the session that ran.  The state does not depend on n_streams or on how
+ * the session that wrote it was launched, with one exception: the lookahead and the sequential schedule make the
+ * same decisions but round z differently (a forward solve against the bordered factor row; mk_session_set_lookahead),
+ * so a chain written under one and continued under the other would agree with neither to the last bit.  The
+ * schedule is therefore part of what a started chain is ("before the first mk_session_run only" above): the
+ * checkpoint records it, and a restore at 0 < iteration < n.samples puts the session on the schedule that wrote
+ * the state, whatever it was made with (mk_session_lookahead reports it; at iteration 0 and n.samples the
+ * session keeps its own).  A session of several stream groups cannot run the lookahead schedule: a state
+ * written mid-chain under it is MK_E_ARG there, by name -- a different chain is never continued.
+ * mk_session_digest: the digests of the session's factors now, [n_subsets q][MK_CKPT_NDIGEST].
+ * mk_digest: the digest of n_words caller-given host words on `device` (uploaded in chunks; MK_DIGEST_CHUNK
+ * words per chunk, default 2^25), by the kernel the sessions use (k_state_digest).
+ * Kernel-stat kind 21: the digest launches -- launches and ms, always timed, 0 launches unless a checkpoint,
+ * restore or digest call is made. */
+#define MK_CKPT_NFIELDS 24
+#define MK_CKPT_NDIGEST 4
+#define MK_DIGEST_L 0
+#define MK_DIGEST_WINV 1
+#define MK_DIGEST_W 2
+#define MK_DIGEST_QB 3
+typedef struct mk_checkpoint {
+  void* field[MK_CKPT_NFIELDS]; /* field f: [count] x words[f] 8-byte words; NULL only where words[f] = 0 */
+  uint64_t* digests;            /* [count q][MK_CKPT_NDIGEST]                                             */
+  int32_t lookahead;            /* the schedule that wrote the state: mk_session_lookahead (set by checkpoint) */
+} mk_checkpoint;
+int mk_session_checkpoint_layout(const mk_session* s, int32_t iteration, int64_t* words);
+int mk_session_checkpoint(mk_session* s, int32_t first, int32_t count, mk_checkpoint* out);
+int mk_session_restore(mk_session* s, int32_t iteration, const int64_t* words, const mk_checkpoint* in);
+int mk_session_digest(mk_session* s, uint64_t* out);
+int mk_digest(const void* words, int64_t n_words, int32_t device, uint64_t* out);
+/* What the last restore cost, by device events: the re-derivation (candidates, Cholesky, inverse, kriging
+ * refresh), the digests, and the uploads (host clock).  MK_E_ARG unless the session was restored. */
+int mk_session_restore_stats(const mk_session* s, double* ms_derive, double* ms_digest, double* ms_upload);
 
 const char* mk_last_error(void);
 int mk_device_count(void);

@@ -7,7 +7,7 @@ this package is the host-side mirror of the reference's R interface
 """
 from ._lib import MkError, load  # noqa: F401
 from .session import (SamplerConfig, Session, chain_diagnostics, cholesky_batched, combine,  # noqa: F401
-                      correlation_batched, correlation_cross_batched, loo_compare, map_grid, psis_loo, score_grid)
+                      correlation_batched, correlation_cross_batched, digest, loo_compare, map_grid, psis_loo, score_grid)
 from .spbayes import (load_fit, spDiag, spDiagnostics, spLoo, spMaps, spMvGLM, spPairs, spPredict, spRegions,  # noqa: F401
                       spValidate)
 from .glm import glm_binomial  # noqa: F401

@@ -8,11 +8,11 @@ CSRC = os.path.join(PKG_DIR, "csrc")
 LIB_PATH = os.path.join(PKG_DIR, "libmk.so")
 SOURCES = ["mk_linalg.hip", "mk_mcmc.hip", "mk_init.hip", "mk_post.hip", "mk_api.hip", "mk_pool.hip", "mk_schedule.hip",
            "mk_krig.hip", "mk_summary.hip", "mk_parity.hip", "mk_diag.hip", "mk_criteria.hip", "mk_loo.hip",
-           "mk_scores.hip", "mk_maps.hip", "mk_pairs.hip", "mk_regions.hip", "mk_import.hip", "mk_multi.hip", "mk_watch.hip",
+           "mk_scores.hip", "mk_maps.hip", "mk_pairs.hip", "mk_regions.hip", "mk_import.hip", "mk_checkpoint.hip", "mk_multi.hip", "mk_watch.hip",
            "mk_variogram.hip", "mk_rsample.cpp"]
 HEADERS = ["mk_common.hpp", "mk_types.hpp", "mk_gemm.hpp", "mk_corr.hpp", "mk_kernels.hpp", "mk_internal.hpp",
            "mk_session.hpp", "mk_tilefill.hpp", "mk_regionspec.hpp", "mk_regionchunk.hpp", "mk_variogramspec.hpp",
-           "mk_importspec.hpp"]
+           "mk_importspec.hpp", "mk_checkpointspec.hpp"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wno-unused-value",
          "-Wno-unused-result"]
 

@@ -43,6 +43,11 @@ REGIONS_EXACT, REGIONS_INTERP = 0, 1    # MK_REGIONS_EXACT, MK_REGIONS_INTERP: t
 REGION_ROUTE_NAMES = ["exact", "interpolated"]
 VG_MAXBINS = 64        # MK_VG_MAXBINS: variogram bins at most
 VG_MAXQ = 4            # MK_VG_MAXQ: outcomes of a variogram at most
+CKPT_NFIELDS = 24      # MK_CKPT_NFIELDS: the fields of mk_checkpoint, in CKPT_FIELDS' order
+CKPT_FIELDS = ["beta", "theta", "w", "eta", "tune", "acc", "u", "z", "Z", "logdetR", "quad", "A_full", "Ainv", "notpd",
+               "crit_acc", "crit_part", "crit_sbeta", "samples", "w_samples", "acc_hist", "kz", "kth", "kA", "w_pred"]
+CKPT_NDIGEST = 4       # MK_CKPT_NDIGEST: the digests per (subset, outcome) pair, in DIGEST_NAMES' order
+DIGEST_NAMES = ["L", "Winv", "W", "QB"]
 
 _dp = ctypes.POINTER(ctypes.c_double)
 _ip = ctypes.POINTER(ctypes.c_int32)
@@ -145,6 +150,11 @@ class Chain(ctypes.Structure):
     _fields_ = [("samples", _dp), ("w_samples", _dp), ("n_w", ctypes.c_int32), ("acceptance", _dp)]
 
 
+class Checkpoint(ctypes.Structure):
+    _fields_ = [("field", ctypes.c_void_p * CKPT_NFIELDS), ("digests", ctypes.POINTER(ctypes.c_uint64)),
+                ("lookahead", ctypes.c_int32)]
+
+
 # int (*mk_progress_fn)(void* user, int32_t iterations, int32_t n_samples)
 PROGRESS_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32)
 
@@ -212,6 +222,13 @@ EXPORTS = {
     "mk_session_import_chain": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(Chain)]),
     "mk_session_imported": (ctypes.c_int32, [ctypes.c_void_p]),
     "mk_session_import_stats": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64), _dp, _dp]),
+    "mk_session_checkpoint_layout": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(ctypes.c_int64)]),
+    "mk_session_checkpoint": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(Checkpoint)]),
+    "mk_session_restore": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(ctypes.c_int64),
+                                          ctypes.POINTER(Checkpoint)]),
+    "mk_session_digest": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64)]),
+    "mk_digest": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.POINTER(ctypes.c_uint64)]),
+    "mk_session_restore_stats": (ctypes.c_int, [ctypes.c_void_p, _dp, _dp, _dp]),
     "mk_session_destroy": (None, [ctypes.c_void_p]),
     "mk_session_count": (ctypes.c_int32, []),
     "mk_fit_predict_batched": (ctypes.c_int, [ctypes.POINTER(Problem), ctypes.POINTER(Config), ctypes.POINTER(Outputs)]),

@@ -14,6 +14,7 @@
 //   mk_pairs.hip     cross-outcome prediction (co-occurrence and contrast of two outcomes): the kernels, the entry points
 //   mk_regions.hip   areal prediction (regional prevalence from joint kriging draws): the kernels, the entry points
 //   mk_import.hip    sessions from a recorded chain: the kernels, the upload, the entry points
+//   mk_checkpoint.hip  checkpoints: the state out and in, the digest kernel, the entry points
 //
 // What the six result sinks above share is here and in mk_tilefill.hpp: EventTimer (their launches' price),
 // TileFill (which tiles a tiled session's buffer holds, over which kept window), results_entry (the checks a
@@ -82,7 +83,7 @@ static inline double matern_span_pt(const double* b, const double* t) {
                     std::fmax(std::fabs(b[3] - t[2]), std::fabs(t[3] - b[2])));
 }
 
-constexpr int NKSTAT = 21;
+constexpr int NKSTAT = 22;
 // KS_CHOL_UPDATE: the 128-tile panel-update launches (k_chol_update<128>); KS_CHOL_UPDATE_SUB:
 // the 64- / 32-sub-tile ones (small grids).  Together: the roofline kernel k_chol_update.
 // KS_UPDATE_BUSY: both, with the time of launches that overlap (the split schedule's bulk and
@@ -92,7 +93,7 @@ constexpr int NKSTAT = 21;
 // KS_COV: the candidates' covariance assembly (k_cov_candidate, with k_matern_table for Matern).
 enum { KS_CHOL_UPDATE = 0, KS_CHOL_DIAG, KS_CHOL_TRSM, KS_SWEEP, KS_LAUUM, KS_ITER, KS_INV, KS_CHOL_UPDATE_SUB,
        KS_UPDATE_BUSY, KS_PRED_VAR, KS_COV, KS_SWEEP_FALLBACK, KS_KRIG_CHEB, KS_KRIG_FALLBACK, KS_DIAG, KS_CRIT,
-       KS_SCORE, KS_MAPS, KS_PAIRS, KS_REGIONS, KS_LOO };
+       KS_SCORE, KS_MAPS, KS_PAIRS, KS_REGIONS, KS_LOO, KS_CKPT };
 // KS_KRIG_CHEB: tiles kriged by phi interpolation (predict_tile_cheb): launches = tiles, flops = exact
 // s evaluations (one per (subset, outcome) pair and node or check point), total_ms = the largest check
 // difference seen over all pairs and sites (not a time).  KS_KRIG_FALLBACK: tiles whose check failed
@@ -119,6 +120,9 @@ enum { KS_CHOL_UPDATE = 0, KS_CHOL_DIAG, KS_CHOL_TRSM, KS_SWEEP, KS_LAUUM, KS_IT
 // KS_LOO: the PSIS-LOO launches (k_loo_terms and k_loo_psis per chunk of subsets, k_loo_finish and k_loo_total
 // per mk_session_loo), bracketed by events whether or not the profiler is on; none are made unless
 // mk_session_loo is called.
+// KS_CKPT: the state-digest launches (k_state_digest and k_digest_reduce per factor buffer of a checkpoint, a
+// restore or mk_session_digest), bracketed by events whether or not the profiler is on; none are made unless one
+// of those calls is.
 // KS_SWEEP_FALLBACK: launches = (subset, iteration) sweeps k_sweep_mg refused admission and its
 // k_sweep fallback ran (counted on the device, read at the end of every mk_session_run; no timing).
 
@@ -362,6 +366,12 @@ struct Import {
   int batch = 0;               // states per pass over W (k_import_z's B)
 };
 
+// mk_checkpoint.hip.  A state restored by mk_session_restore, and what the restore cost.
+struct Restore {
+  bool done = false;
+  double ms_derive = 0.0, ms_digest = 0.0, ms_upload = 0.0;
+};
+
 }  // namespace mk
 
 struct mk_session {
@@ -404,6 +414,7 @@ struct mk_session {
   mk::Pairs pairs;
   mk::Regions regions;
   mk::Import imp;
+  mk::Restore rst;
   std::vector<double> ct_h;      // the current test sites on the host, x then y (the regions' coincidence check)
   mk_diagnostics diag_sink{};           // mk_session_set_diagnostics: filled by every tile replay while diag_on
   bool diag_on = false;

@@ -26,6 +26,7 @@ KS_MAPS = 17      # the posterior-map launches (always timed; 0 launches unless 
 KS_PAIRS = 18     # the cross-outcome launches (always timed; 0 launches unless pairs were asked for)
 KS_REGIONS = 19   # the areal-prediction launches (always timed; 0 launches unless regions were attached)
 KS_LOO = 20       # the PSIS-LOO launches (always timed; 0 launches unless loo() was called)
+KS_CKPT = 21      # the state-digest launches (always timed; 0 launches unless checkpoint(), restore() or digest() ran)
 
 
 def _f64(a):
@@ -276,6 +277,79 @@ class Session:
         n, a, b = ctypes.c_int64(), ctypes.c_double(), ctypes.c_double()
         check(self._lib.mk_session_import_stats(self._h, ctypes.byref(n), ctypes.byref(a), ctypes.byref(b)))
         return dict(factorisations=n.value, ms_factor=a.value, ms_z=b.value)
+
+    def _ckpt_words(self, iteration=-1):
+        w = np.zeros(_lib.CKPT_NFIELDS, dtype=np.int64)
+        check(self._lib.mk_session_checkpoint_layout(self._h, int(iteration), w.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))))
+        return w
+
+    def checkpoint(self, first=0, count=None):
+        """The state of subsets [first, first + count) after the iterations done so far (mk_session_checkpoint;
+        the fields are listed in include/mk.h): a dict of numpy arrays -- 'iteration', 'words' (the words per
+        subset of every field), every field of _lib.CKPT_FIELDS as (count, words) float64 ('notpd': int64) and
+        'digests', (count q, 4) uint64, the digests of the pairs' factor buffers L, Winv, W, QB.  restore() of a
+        session made over the same subsets and configuration takes it back and run() continues the chain bit for
+        bit.  Only the rows of the record that exist are held."""
+        count = self.S - int(first) if count is None else int(count)
+        first = int(first)
+        if first < 0 or count < 1 or first + count > self.S:
+            raise ValueError(f"error: checkpoint of subsets ({first}, {count}) is outside the session's {self.S} subsets")
+        words = self._ckpt_words()
+        st = {"iteration": np.array(self.iteration), "words": words}
+        c = _lib.Checkpoint()
+        for f, name in enumerate(_lib.CKPT_FIELDS):
+            st[name] = np.zeros((count, int(words[f])), dtype=np.int64 if name == "notpd" else np.float64)
+            c.field[f] = st[name].ctypes.data if words[f] else None
+        st["digests"] = np.zeros((count * self.q, _lib.CKPT_NDIGEST), dtype=np.uint64)
+        c.digests = st["digests"].ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))
+        check(self._lib.mk_session_checkpoint(self._h, first, count, ctypes.byref(c)))
+        st["lookahead"] = np.array(bool(c.lookahead))      # the schedule that wrote the state
+        return st
+
+    def restore(self, state):
+        """A checkpoint()'s state into this session, which must be as it was created: no iteration run, nothing
+        imported, over the subsets the state holds and the configuration of the session that wrote it
+        (mk_session_restore).  Afterwards `iteration` is the state's and run() continues the chain, on the schedule
+        that wrote the state when it was written mid-chain (`lookahead` reports it); at n_samples
+        the outputs and sinks are served.  The factors are re-derived from the restored theta and their digests
+        compared with the state's: MkError names the pair and the buffer of a mismatch, and the session is then
+        unusable.  MkError names the subset and the field of a size or a value the restore refuses."""
+        for k in ["iteration", "words", "digests", "lookahead"] + _lib.CKPT_FIELDS:
+            if k not in state:
+                raise ValueError(f"error: the state lacks the key '{k}'")
+        words = np.ascontiguousarray(np.asarray(state["words"], dtype=np.int64).reshape(-1))
+        if words.shape != (_lib.CKPT_NFIELDS,):
+            raise ValueError(f"error: the state's key 'words' has shape {words.shape}, not ({_lib.CKPT_NFIELDS},)")
+        c = _lib.Checkpoint()
+        keep = []
+        for f, name in enumerate(_lib.CKPT_FIELDS):
+            a = np.ascontiguousarray(np.asarray(state[name], dtype=np.int64 if name == "notpd" else np.float64))
+            if a.shape != (self.S, int(words[f])):
+                raise ValueError(f"error: the state's key '{name}' has shape {a.shape}; the session's {self.S} subsets and "
+                                 f"the key 'words' give {(self.S, int(words[f]))}")
+            keep.append(a)
+            c.field[f] = a.ctypes.data if a.size else None
+        dg = np.ascontiguousarray(np.asarray(state["digests"], dtype=np.uint64))
+        if dg.shape != (self.S * self.q, _lib.CKPT_NDIGEST):
+            raise ValueError(f"error: the state's key 'digests' has shape {dg.shape}, not {(self.S * self.q, _lib.CKPT_NDIGEST)}")
+        c.digests = dg.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))
+        c.lookahead = int(bool(state["lookahead"]))
+        check(self._lib.mk_session_restore(self._h, int(state["iteration"]), words.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
+                                           ctypes.byref(c)))
+
+    def digest(self):
+        """(S q, 4) uint64: the digests of every (subset, outcome) pair's factor buffers now -- L, Winv, W, QB over
+        the region later iterations read (mk_session_digest; QB is 0 where the session's sweep keeps none)."""
+        out = np.zeros((self.S * self.q, _lib.CKPT_NDIGEST), dtype=np.uint64)
+        check(self._lib.mk_session_digest(self._h, out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))))
+        return out
+
+    def restore_stats(self):
+        """What restore() cost in milliseconds (mk_session_restore_stats): the re-derivation of the factors, the
+        digests (both by device events) and the uploads (host clock)."""
+        a, b, c = ctypes.c_double(), ctypes.c_double(), ctypes.c_double()
+        check(self._lib.mk_session_restore_stats(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)))
+        return dict(ms_derive=a.value, ms_digest=b.value, ms_upload=c.value)
 
     def set_test_sites(self, coords_test, x_test=None):
         """Kriging sites for the next outputs() of a session created with predict_tile > 0
@@ -604,6 +678,20 @@ def combine(grids, device=0, mean=True):
     fn = lib.mk_combine if mean else lib.mk_combine_sum
     check(fn(dptr(g.reshape(K, -1)), K, int(np.prod(g.shape[1:])), dptr(out), int(device)))
     return out
+
+
+def digest(words, device=0):
+    """The 64-bit state digest of a sequence of 8-byte words on the device (mk_digest; the kernel the sessions'
+    checkpoints use): D = sum_i mix(x_i + (i + 1) 0x9E3779B97F4A7C15) mod 2^64, mix the splitmix64 finaliser.
+    words: an array of float64, int64 or uint64, taken in C order by its bit patterns.  0 for no words."""
+    lib = _lib.load()
+    a = np.asarray(words)
+    if a.dtype not in (np.float64, np.int64, np.uint64):
+        raise ValueError(f"error: digest takes 8-byte words (float64, int64 or uint64), not {a.dtype}")
+    a = np.ascontiguousarray(a).reshape(-1)
+    out = ctypes.c_uint64()
+    check(lib.mk_digest(a.ctypes.data if a.size else None, int(a.size), int(device), ctypes.byref(out)))
+    return int(out.value)
 
 
 def chain_diagnostics(x, axis=0, device=0):

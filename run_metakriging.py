@@ -115,6 +115,19 @@ def main():
                     help="skip the partition, the start-value glm and the MCMC: load DIR/session_0.npz (--save-fit), "
                          "krige this run's test sites from its recorded chain, combine and summarise as usual.  One "
                          "process; not with --devices")
+    ap.add_argument("--checkpoint", default=None, metavar="DIR",
+                    help="write the running chain's state to DIR/shard<first subset>.npz (fitfile.save_checkpoint: the "
+                         "data, the configuration and everything a later process needs to continue the chain bit for "
+                         "bit), once at the end of the chain and, with --checkpoint-every, on the way; each write replaces "
+                         "the file atomically.  Not with --devices, --save-fit or --from-fit.  Off by default: without it "
+                         "nothing about a run changes")
+    ap.add_argument("--checkpoint-every", type=int, default=0, metavar="N",
+                    help="with --checkpoint: also write after every N amcmc batches")
+    ap.add_argument("--resume", default=None, metavar="DIR",
+                    help="continue the chain of DIR/shard<first subset>.npz (--checkpoint) to n.samples instead of "
+                         "starting one, then go on with the flow as usual; the file must hold this run's subsets and "
+                         "configuration (the first key that differs is named).  Not with --devices, --save-fit or "
+                         "--from-fit")
     a = ap.parse_args()
     a.map_thresholds = None if a.maps is None else [float(u) for u in a.maps.split(",") if u.strip()]
     a.pair_thresholds = None if a.pairs is None else [float(u) for u in a.pairs.split(",") if u.strip()]
@@ -130,6 +143,14 @@ def main():
         a.variogram = 15
     if a.save_fit is not None and a.from_fit is not None:
         ap.error("--save-fit and --from-fit: a run either makes the chain and saves it, or loads it")
+    if a.checkpoint_every and a.checkpoint is None:
+        ap.error("--checkpoint-every needs --checkpoint DIR")
+    if a.checkpoint_every < 0:
+        ap.error("--checkpoint-every counts amcmc batches: 0 (the end of the chain alone) or more")
+    if (a.checkpoint is not None or a.resume is not None) and (a.devices is not None or a.save_fit is not None or
+                                                               a.from_fit is not None):
+        ap.error("--checkpoint and --resume run in the plain path (one process per GPU), not with --devices, --save-fit or "
+                 "--from-fit")
     if a.devices is not None:
         if a.save_fit is not None or a.from_fit is not None:
             ap.error("--save-fit and --from-fit run in the plain path (one process), not with --devices")
@@ -204,7 +225,13 @@ def main():
     if subs:
         # one process, fused kriging: x.test goes in as MK.R:87 passes it, p.predict comes out
         x_test = d["x_test"] if ((world == 1 and not big) or need_p) else None   # MK.R:108
-        if not kept_states:
+        ckpt_file = f"shard{lo}.npz"
+        if a.resume is not None:                  # the chain of an earlier process, continued below
+            ses = mk.fitfile.load_checkpoint(os.path.join(a.resume, ckpt_file), device=local, data=subs, cfg=cfg,
+                                             record_w=a.loo, criteria=a.criteria)
+            if rank == 0:
+                print(f"resumed at iteration {ses.iteration}/{cfg.n_samples}", file=sys.stderr, flush=True)
+        elif not kept_states:
             ses = mk.Session(subs, cfg, coords_test=d["coords_test"], subset_base=lo, device=local, x_test=x_test,
                              criteria=a.criteria, record_w=a.loo)     # --loo replays the recorded chain
         else:     # no test sites at creation: the session keeps every kept state; --criteria replays the recorded chain
@@ -215,10 +242,17 @@ def main():
             ses.set_validation(d["y_test"])
         if a.pair_thresholds is not None:         # filled now (fused) or by the tile replays
             ses.set_pairs(a.pair_thresholds)
-        for b in range(cfg.n_batch if a.from_fit is None else 0):   # progress every n.report = 10 batches (MK.R:84)
-            ses.run(cfg.batch_length)
-            if rank == 0 and (b + 1) % 10 == 0:
-                print(f"batch {b + 1}/{cfg.n_batch}  {time.perf_counter() - t2:.1f}s", file=sys.stderr, flush=True)
+        it = ses.iteration if a.from_fit is None else cfg.n_samples     # > 0 after --resume, mid-batch where it stopped
+        while it < cfg.n_samples:                 # progress every n.report = 10 batches (MK.R:84)
+            step = cfg.batch_length - it % cfg.batch_length
+            ses.run(step)
+            it += step
+            b = it // cfg.batch_length
+            if rank == 0 and b % 10 == 0:
+                print(f"batch {b}/{cfg.n_batch}  {time.perf_counter() - t2:.1f}s", file=sys.stderr, flush=True)
+            if a.checkpoint is not None and ((a.checkpoint_every and b % a.checkpoint_every == 0) or it == cfg.n_samples):
+                os.makedirs(a.checkpoint, exist_ok=True)
+                mk.fitfile.save_checkpoint(ses, os.path.join(a.checkpoint, ckpt_file))
         if a.save_fit is not None:
             os.makedirs(a.save_fit, exist_ok=True)
             mk.fitfile.save_session(ses, os.path.join(a.save_fit, "session_0.npz"))
